@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- objects/sec into one 4k x 4k LSST CCD (photon-shooting path), BASELINE.json's metric.
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c3b|c4|c5|fft|fftx|fftxs] [--no-cpu-baseline] [--no-extra-configs]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c3b|c4|c5|fft|fftx|fftxs] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-extra-configs] [--no-cold]]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything else the line
+has carried: the CPU baselines with their oracle parity check, the other BASELINE configs (extra.configs), the cold and
+end-to-end timings and the extra steps that time the pixel search of the brighter-fatter rounds.  --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample of a large CCD image).
 
 One step = one pass of the hot path over the whole synthetic instance catalog with
 the object table already resident in HBM.  For N > 1 there is one rank per GPU: either started by
@@ -40,12 +46,17 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default=os.environ.get("IMSIM_BENCH_CONFIG", "c3"))
     ap.add_argument("--n-objects", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: CPU baselines and parity, the other configs, cold / end-to-end timings, "
+                         "the extra steps of the pixel-search roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cpu-allcore", action="store_true", help="skip the all-core CPU leg")
     ap.add_argument("--no-cold", action="store_true", help="skip the cold (plan + upload + run) render timing")
     ap.add_argument("--cpu-sample", type=int, default=0, help="objects in the one-core CPU-baseline sample")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the short runs of the other BASELINE configs (extra.configs of the default c3 line)")
+                    help="skip the short runs of the other BASELINE configs (extra.configs of the --full c3 line)")
     return ap.parse_args()
 
 
@@ -122,8 +133,8 @@ def extra_configs(budget_s=420.0):
         if left < 10.0:
             out[name] = {"skipped": "time budget of the extra configs used up"}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(n_steps), "--warmup", str(n_warm), "--no-cold",
-               "--no-cpu-allcore", "--no-extra-configs"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", name, "--steps", str(n_steps), "--warmup", str(n_warm),
+               "--no-cold", "--no-cpu-allcore", "--no-extra-configs"]
         if sample:
             cmd += ["--cpu-sample", str(sample)]
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "IMSIM_BENCH_CONFIG")}
@@ -194,7 +205,7 @@ def main():
     cfg = configs.BENCH_CONFIGS[args.config]
     # The CPU legs run FIRST, before this process initialises the GPU (the all-core leg forks workers).  Building the
     # scene / catalog is host-only, except C3b whose phase screens are generated on the GPU.
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     cpu_first = want_cpu and not cfg.get("scene_needs_gpu", False)
 
     # IMS_BENCH_SHARE_GPU=1 is a dry run of the multi-rank path on a box with ONE GPU (all ranks on cuda:0, gloo instead
@@ -217,7 +228,7 @@ def main():
 
     # the other BASELINE configs, each a short child run with its own oracle parity flag -- before this process touches the GPU
     extra_cfg = None
-    if (rank == 0 and world == 1 and args.config == "c3" and not args.no_extra_configs and not args.no_cpu_baseline
+    if (args.full and rank == 0 and world == 1 and args.config == "c3" and not args.no_extra_configs and not args.no_cpu_baseline
             and not args.n_objects and os.environ.get("IMS_BENCH_EXTRA", "1") != "0"):
         extra_cfg = extra_configs()
 
@@ -350,6 +361,8 @@ def main():
         elif rank == 0:
             np.savez(dump, image=renderer.image.cpu().numpy(),
                      integer_counts_ok=np.array([parallel.integer_counts_ok(renderer.image, 1)]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step, renderer.image, rank, world, dist)
 
     n_total_obj = len(objects)
     fft_mask = getattr(objects, "fft_mask", None)           # a focal plane's FFT-drawn objects shoot no photons
@@ -423,7 +436,7 @@ def main():
     # The other large kernel of a step with brighter-fatter chains is the pixel search of the rounds (k_accumulate_round): its
     # launches are timed the same way in a few extra steps, and the line names as `roofline.kernel` whichever of the two has
     # the larger summed launch time per step -- the kernel that is dominant in the shipped kernel trace.
-    if have_ms and 4 in getattr(step, "timed", {}) and step.timed[4][0] > 0 and cfg["timed_kernel"] == 2:
+    if args.full and have_ms and 4 in getattr(step, "timed", {}) and step.timed[4][0] > 0 and cfg["timed_kernel"] == 2:
         extra_steps = 3
         lib.ims_enable_timing(4)
         for _ in range(extra_steps):
@@ -477,7 +490,7 @@ def main():
         out["exchange"] = ("libimsim_hip.so over RCCL (ims_reduce_image / ims_allreduce_delta)" if parallel._LIBRARY_COMM[0] is not None
                            else ("torch.distributed " + dist.get_backend()))
 
-    if rank == 0 and world == 1 and not args.no_cold and ("cold" in cfg or "end_to_end" in cfg):
+    if args.full and rank == 0 and world == 1 and not args.no_cold and ("cold" in cfg or "end_to_end" in cfg):
         out["extra"] = cfg["cold"](scene, objects, device) if "cold" in cfg else {}
         # host side of LSST_SiliconBuilder.setup for the whole catalog (Poisson fluxes, stamp sizes, local WCS, DCR angles)
         out["extra"]["object_table_ms"] = timing.get("object_table_ms")
@@ -500,6 +513,46 @@ def main():
         os.write(JSON_FD[0], (json.dumps(out) + "\n").encode())
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()
+
+
+DUMP_WHOLE_BYTES = 48 << 20     # a CCD image up to this size is written whole ...
+DUMP_SAMPLE = 1 << 22           # ... a larger one as its values at this many pixels (32 MiB in f64), fixed by DUMP_SEED
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, step, image, rank, world, dist):
+    """--dump-outputs: what the last timed step left for its caller, as float64 .npy files of at most 64 MB in all, so that two
+    builds can be compared output for output.  A CCD image (the f64 accumulation image, reduced onto rank 0): its row and
+    column sums, and the image itself or its values at a fixed, seeded sample of pixels.  A focal plane: the host-side
+    checksum of every CCD's float32 image, by CCD number, gathered from whichever rank rendered it."""
+    checks = getattr(step, "checksums", None)
+    if checks is not None:
+        box = [None] * world
+        if world > 1:
+            dist.gather_object(dict(checks), box if rank == 0 else None, dst=0)
+        else:
+            box = [dict(checks)]
+        if rank != 0:
+            return
+        merged = {}
+        for part in box:
+            merged.update(part)
+        dets = sorted(merged)
+        arrays = {"ccd_ids": np.array(dets, dtype=np.float64),
+                  "ccd_checksums": np.array([merged[d] for d in dets], dtype=np.float64)}
+    else:
+        if rank != 0:
+            return
+        img = image.cpu().numpy().astype(np.float64, copy=False)
+        arrays = {"image_row_sums": img.sum(axis=1), "image_col_sums": img.sum(axis=0)}
+        if img.nbytes <= DUMP_WHOLE_BYTES:
+            arrays["image"] = img
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(img.size, size=DUMP_SAMPLE, replace=False))
+            arrays["image_sample"] = img.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def profile_entry(config, kernel, world):

@@ -25,7 +25,7 @@ def test_every_bench_config_has_current_counters_and_both_floors():
     from imsim_amd import configs
     table = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
     names = {c[0] for c in bench.EXTRA_CONFIGS} | {"c3"}
-    assert names == set(configs.BENCH_CONFIGS), "every bench config is on the default line (extra.configs)"
+    assert names == set(configs.BENCH_CONFIGS), "every bench config is on the --full line (extra.configs)"
     for name in sorted(names):
         step = table[name]["_step"]
         assert step["sq_source"].startswith("profiles/round6_"), (name, step["sq_source"])

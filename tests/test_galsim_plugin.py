@@ -97,8 +97,9 @@ def test_names_are_registered_and_the_image_builder_renders_the_requested_ccd():
 def test_every_name_of_the_reference_is_registered_and_its_default_config_passes_the_input_and_output_stages():
     """input, object, value, output, extra-output, WCS, bandpass and SED types of imSim are all known to GalSim's
     registries once the module is imported, so that a reference YAML (`modules: [imsim_amd.galsim_plugin]` in place of
-    `modules: [imsim]`) gets through ProcessInput and the output stage to the image builder: a walk over the reference's own
-    config/imsim-config-instcat.yaml (template chain resolved by imsim_amd.config.load_config) with the stand-in."""
+    `modules: [imsim]`) gets through ProcessInput and the output stage to the image builder: a walk over tests/data's config in
+    the shape of the reference's config/imsim-config-instcat.yaml (template chain resolved by imsim_amd.config.load_config) with
+    the stand-in."""
     import os
     from imsim_amd import config as our_config
     gs, cfg, reg = _fake_galsim()
@@ -116,13 +117,8 @@ def test_every_name_of_the_reference_is_registered_and_its_default_config_passes
     assert set(reg["bandpass"]) == {"RubinBandpass"} and set(reg["sed"]) == {"InstCatSED"}
     assert ("output", "LSST_CCD") in done
     here = os.path.dirname(os.path.abspath(__file__))
-    ref_cfg = "/root/reference/config/imsim-config-instcat.yaml"
-    if os.path.isfile(ref_cfg):                                 # the reference's own file where it is present (not on the GPU box)
-        base = our_config.load_config(ref_cfg, template_dirs=["/root/reference/config"],
-                                      overrides={"input.instance_catalog.file_name": os.path.join(here, "golden", "example_instcat_subset.txt")})
-    else:
-        base = our_config.load_config(os.path.join(here, "data", "test-config-instcat.yaml"), template_dirs=[os.path.join(here, "data")],
-                                      overrides={"input.instance_catalog.file_name": os.path.join(here, "golden", "example_instcat_subset.txt")})
+    base = our_config.load_config(os.path.join(here, "data", "test-config-instcat.yaml"), template_dirs=[os.path.join(here, "data")],
+                                  overrides={"input.instance_catalog.file_name": os.path.join(here, "golden", "example_instcat_subset.txt")})
     base["input"] = {k: v for k, v in base["input"].items() if v not in ("", None)}
     for key in base["input"]:
         assert key in reg["input"], key

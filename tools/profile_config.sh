@@ -1,7 +1,7 @@
 #!/bin/bash
 # Every judged measurement of ONE bench config on the GPU box (round 6: every config current, same passes for all of them):
 #   gpurun -- 'bash tools/profile_config.sh <tag> <config>'
-#   1  the bench line as `python bench.py --config X` prints it                      -> gpurun_out/<tag>_<cfg>_bench.json
+#   1  the bench line as `python bench.py --full --config X` prints it               -> $O/<tag>_<cfg>_bench.json
 #   2  timeout ${PASS_TIMEOUT:-420} rocprofv3 --kernel-trace --stats                                              -> <tag>_<cfg>_kernel_stats.txt
 #   3  HBM traffic: FETCH_SIZE and WRITE_SIZE in separate --pmc passes               -> <tag>_<cfg>_hbm_pmc.{txt,json}
 #   4  SQ: instructions, waves, wave / wait cycles                                   -> <tag>_<cfg>_sq_pmc.{txt,json}
@@ -16,9 +16,9 @@ O=$R/gpurun_out
 mkdir -p $O
 S=2; W=1
 case $CFG in c2) S=5;; fft) S=10; W=3;; fftx|fftxs) S=1;; c5) S=1; export IMS_C5_CCDS=${IMS_C5_CCDS_PMC:-48};; esac
-ARGS="--config $CFG --steps $S --warmup $W --no-cpu-baseline --no-cold --no-extra-configs"
+ARGS="--full --config $CFG --steps $S --warmup $W --no-cpu-baseline --no-cold --no-extra-configs"
 if [ -z "$SKIP_BENCH" ]; then
-  ( unset IMS_C5_CCDS; timeout 1500 python3 $R/bench.py --config $CFG --no-extra-configs > $O/${TAG}_${CFG}_bench.json 2> $O/${TAG}_${CFG}_bench.err )
+  ( unset IMS_C5_CCDS; timeout 1500 python3 $R/bench.py --full --config $CFG --no-extra-configs > $O/${TAG}_${CFG}_bench.json 2> $O/${TAG}_${CFG}_bench.err )
   cut -c1-400 $O/${TAG}_${CFG}_bench.json
 fi
 cd /tmp && export TMPDIR=/tmp
