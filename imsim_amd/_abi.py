@@ -246,8 +246,31 @@ class PlanSizes(C.Structure):
 
 Tuning = tuning.Tuning          # ims_tuning_t lives with the one module that fills it
 
+
+IMS_OPD_REF_CHIEF, IMS_OPD_REF_MEAN = 0, 1
+IMS_OPD_MAX_J = 66
+IMS_OPD_NPOW = 11
+IMS_OPD_MAX_NX = 4096
+
+
+class Opd(C.Structure):
+    """ims_opd_t: the rays, reference and Zernike fit of one call of ims_opd (opd.compute fills it)"""
+    _fields_ = [("n_fields", c_i32), ("nx", c_i32), ("reference", c_i32), ("jmax", c_i32), ("dirs", c_vp),
+                ("dx", c_d), ("wavelength", c_d), ("sphere_radius", c_d), ("r_outer", c_d), ("eps", c_d),
+                ("zk_poly", c_vp), ("zk_m", c_vp), ("opd", c_vp), ("zk_ata", c_vp), ("zk_atw", c_vp), ("scratch", c_vp)]
+
+
+def opd_scratch_bytes(n_fields, nx, jmax):
+    """IMS_OPD_SCRATCH_BYTES of include/imsim_hip.h"""
+    npix = nx * nx
+    blocks, chunks = (npix + 255) // 256, (npix + 4095) // 4096
+    return 8 * n_fields * (10 * (npix + 1) + 6 * blocks + 4 + chunks * (jmax * (jmax + 3) // 2))
+
 STRUCTS = [Object, RadialTables, LinTables, PsfComponent, Op, Surface, TanSip, Optics, BfSlot, Sensor, Photons,
            RenderParams, PlanItem, Atmosphere, FftObject, FftParams, Readout, Chain, Catalog, ObjectMeta, PlanInput, PlanSizes, Tuning]
+# ims_opd_t is ims_struct_size(23) of the library but not in STRUCTS: the CPU oracle checks its own struct sizes against STRUCTS
+# and has no OPD path, so the one struct only libimsim_hip.so knows is checked by its index alone
+OPD_STRUCT_INDEX = 23
 
 # every symbol include/imsim_hip.h declares
 EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_info", "ims_known_optics_layout",
@@ -259,7 +282,7 @@ EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_
            "ims_build_object_table", "ims_patch_stamp_sizes", "ims_gather_rows", "ims_parse_instcat_objects", "ims_screen_prepass",
            "ims_plan_lsst_image", "ims_plan_bind", "ims_plan_upload", "ims_plan_run", "ims_plan_run_deferred", "ims_plans_run_joint", "ims_plan_join", "ims_plan_add_realized", "ims_plan_destroy",
            "ims_fft_inverse", "ims_fft_inverse_raw", "ims_fft_spikes_listed", "ims_fft_warm", "ims_comm_unique_id", "ims_comm_init", "ims_comm_destroy", "ims_reduce_image", "ims_allreduce_delta",
-           "ims_count_inexact", "ims_struct_size", "ims_test_math"]
+           "ims_count_inexact", "ims_struct_size", "ims_test_math", "ims_opd"]
 
 _LIB_PATH = tuning.env("IMSIM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libimsim_hip.so")
 _lib = None
@@ -293,6 +316,8 @@ def load():
         got = lib.ims_struct_size(k)
         if got != C.sizeof(st):
             raise ImsimHipError(f"ABI mismatch for {st.__name__}: library {got} bytes, binding {C.sizeof(st)}")
+    if lib.ims_struct_size(OPD_STRUCT_INDEX) != C.sizeof(Opd):
+        raise ImsimHipError(f"ABI mismatch for Opd: library {lib.ims_struct_size(OPD_STRUCT_INDEX)} bytes, binding {C.sizeof(Opd)}")
     lib.ims_shoot_accumulate.argtypes = [C.POINTER(RenderParams), c_vp]
     lib.ims_shoot_photons.argtypes = [C.POINTER(RenderParams), c_vp, C.POINTER(Photons), c_vp]
     lib.ims_apply_ops.argtypes = [C.POINTER(RenderParams), c_vp, C.POINTER(Photons), c_vp]
@@ -355,6 +380,7 @@ def load():
     lib.ims_tuning_defaults.argtypes = [C.POINTER(Tuning)]
     lib.ims_get_tuning.argtypes = [C.POINTER(Tuning)]
     lib.ims_set_tuning.argtypes = [C.POINTER(Tuning)]
+    lib.ims_opd.argtypes = [C.POINTER(Opd), c_vp, c_vp]
     _lib = lib
     return lib
 

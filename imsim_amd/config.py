@@ -19,7 +19,7 @@ import numpy as np
 import yaml
 
 from . import _abi, atm_psf, catalog, configs, diffraction, fft_draw, instcat, lsst_image, optics as opticsmod
-from . import flat, parallel, readout, sensor as sensormod, tables, treerings, tuning
+from . import flat, opd as opdmod, parallel, readout, sensor as sensormod, tables, treerings, tuning
 from .engine import Scene, SensorSetup, make_slots
 from .lsst_image import GalSimConfigError
 
@@ -466,6 +466,66 @@ def _process_outputs(out, ev, res, image_dev, det_name, meta, seed):
         res.files.append(fn)
 
 
+OPD_REQ = ("file_name", "fields")
+OPD_OPT = ("dir", "rotTelPos", "nx", "wavelength", "projection", "sphereRadius", "reference", "eps", "jmax")
+
+
+def parse_opd(opd_cfg, ev):
+    """`output.opd` (imsim/opd.py:59-128) -> keyword arguments of opd.compute (fields and rot_tel_pos in rad; wavelength,
+    sphere_radius and eps None where the telescope / bandpass supply them).  file_name and dir stay unevaluated: they may
+    differ per CCD."""
+    if not isinstance(opd_cfg, dict):
+        raise GalSimConfigError("output.opd must be a dict")
+    for k in opd_cfg:
+        if k not in OPD_REQ and k not in OPD_OPT:
+            raise GalSimConfigError(f"Unexpected attribute {k} found in output.opd")
+    for k in OPD_REQ:
+        if k not in opd_cfg:
+            raise GalSimConfigError(f"Attribute {k} is required in output.opd")
+    fields_cfg = ev.value(opd_cfg["fields"])
+    if not isinstance(fields_cfg, list):
+        raise GalSimConfigError("output.opd.fields must be a list of {thx, thy}")
+    fields = []
+    for d in fields_cfg:
+        if not isinstance(d, dict) or set(d) != {"thx", "thy"}:
+            raise GalSimConfigError("output.opd.fields: every field is {thx: angle, thy: angle}")
+        fields.append((float(ev.value(d["thx"])), float(ev.value(d["thy"]))))
+
+    def opt(key, typ):
+        return typ(ev.value(opd_cfg[key])) if key in opd_cfg else None
+
+    kw = dict(fields=fields, rot_tel_pos=opt("rotTelPos", float) or 0.0, nx=opt("nx", int) or 255,
+              wavelength=opt("wavelength", float), projection=opt("projection", str) or "postel",
+              sphere_radius=opt("sphereRadius", float), reference=opt("reference", str) or "chief", eps=opt("eps", float),
+              jmax=28 if "jmax" not in opd_cfg else opt("jmax", int))
+    try:
+        opdmod.check_params(kw["nx"], kw["projection"], kw["reference"], kw["jmax"])
+    except ValueError as e:
+        raise GalSimConfigError(f"output.opd: {e}") from None
+    return kw
+
+
+def _process_opd(opd_cfg, kw, ev, out, tel, wl_eff, det_nums, res, device):
+    """The maps of the visit's telescope, computed once, written under every distinct file name output.opd.file_name takes
+    over the CCDs of the visit (the same data for each: the OPD ignores per-CCD detector heights, imsim/opd.py:51-57)."""
+    kw = dict(kw)
+    if kw["wavelength"] is None:
+        kw["wavelength"] = wl_eff
+    images = opdmod.compute(tel, device=device, **kw)
+    out_dir = ev.value(opd_cfg.get("dir", out.get("dir", "")))
+    names = []
+    for det in det_nums:
+        ev.vars["det_name"] = det_name_of(det)
+        ev.vars["_sequence_index"] = det
+        fn = os.path.join(str(out_dir), str(ev.value(opd_cfg["file_name"])))
+        if fn not in names:
+            names.append(fn)
+    for fn in names:
+        os.makedirs(os.path.dirname(fn) or ".", exist_ok=True)
+        opdmod.write(fn, images)
+        res.files.append(fn)
+
+
 def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=None, logger=None, rank=0, world=1):
     """galsim.config.Process restricted to this path: reads inputs, then for every requested CCD
     builds the scene and runs the image builder on the GPU.  Returns a ProcessResult.
@@ -501,7 +561,7 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     out = cfg.get("output", {})
     if out.get("type", "LSST_CCD") not in valid_output_types:
         raise GalSimConfigError(f"Invalid output type {out.get('type')}")
-    for k in ("truth", "photon_pooling_truth", "opd", "sag", "process_info", "cosmic_ray_rate"):
+    for k in ("truth", "photon_pooling_truth", "sag", "process_info", "cosmic_ray_rate"):
         if k in out:
             res.ignored.append(f"output.{k}")
     ev.vars["det_name"] = None
@@ -521,6 +581,8 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     if itype not in valid_image_types:
         raise GalSimConfigError(f"Invalid image type {itype}")
     if itype == "LSST_Flat":
+        if "opd" in out:                           # a flat has no telescope to trace
+            res.ignored.append("output.opd")
         return _process_flat(cfg, ev, image, res, device, data_dir)
     stamp_cfg = cfg.get("stamp", {})
     stype = stamp_cfg.get("type", "LSST_Silicon")
@@ -533,6 +595,7 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     band = meta.get("band", "r")
     seed = int(ev.value(image.get("random_seed", meta.get("seed", 0))))
     dets = parallel.shard_ccds(range(first, first + nfiles), rank, world)
+    opd_kw = parse_opd(out["opd"], ev) if "opd" in out else None     # config errors before any GPU work
 
     def prepare(det):
         """Host half of one CCD: scene, catalog, object classification -- everything up to the first GPU call of the CCD
@@ -774,4 +837,12 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
         res.eimages += sub.eimages
         res.raw += sub.raw
         res.files += sub.files
+    if opd_kw is not None and rank == 0:
+        # the visit's telescope and bandpass, as prepare() builds them
+        tel_cfg = inp.get("telescope", {})
+        tel_file = ev.value(tel_cfg.get("file_name", "")) if tel_cfg else ""
+        tel = opticsmod.load_batoid_yaml(tel_file) if tel_file and os.path.isfile(tel_file) else opticsmod.rubin_like_telescope(band)
+        wl, thr = tables.synthetic_r_band()
+        _process_opd(out["opd"], opd_kw, ev, out, tel, tables.effective_wavelength(wl, thr), range(first, first + nfiles), res,
+                     device)
     return res

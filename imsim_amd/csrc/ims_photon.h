@@ -514,8 +514,11 @@ IMS_DEV bool obscured(const ims_surface_t& S, double r2)
 // detector; one step from the conic root for the Rubin mirrors, whose residual is then <= 8e-9 on M2 and <= 2e-10 elsewhere).
 // SHAPE: the surface's form as a compile-time constant (trace_seq: kernels specialised for an optics layout) -- 0 plane,
 // 1 conic with R != 0 and no asphere terms, 2 conic with R != 0 and asphere terms; -1 = read it from the descriptor.
+// PRECISE: the optical-path trace (ims_opd.h) -- the asphere Newton steps until the step |dt| is at f64 resolution of t (at most
+// 10 steps) instead of stopping at |G| <= 1e-8, which leaves nm of sag unresolved: harmless for a photon's position, the whole
+// signal of an OPD map.  false (every photon kernel) is the code above, unchanged.
 constexpr int SH_PLANE = 0, SH_CONIC = 1, SH_ASPHERE = 2;
-template <int SHAPE = -1>
+template <int SHAPE = -1, bool PRECISE = false>
 IMS_DEV bool surf_hit(const ims_surface_t& S, double (&pos)[3], const double (&vel)[3], double (&N)[3], double& nn, double& r2_out)
 {
     const bool is_plane = (SHAPE >= 0) ? (SHAPE == SH_PLANE) : (S.R == 0.0 && S.n_asphere == 0);
@@ -552,7 +555,9 @@ IMS_DEV bool surf_hit(const ims_surface_t& S, double (&pos)[3], const double (&v
     double x = fma(vel[0], t, pos[0]), y = fma(vel[1], t, pos[1]), z = fma(vel[2], t, pz);
     double r2 = fma(x, x, y * y), w = z, dp = 0.0;
     if (is_asphere) {
-        for (int it = 0; it < 6; ++it) {
+        constexpr int n_it = PRECISE ? 11 : 6;
+        bool converged = false;
+        for (int it = 0; it < n_it; ++it) {
             if (it > 0) {
                 x = fma(vel[0], t, pos[0]); y = fma(vel[1], t, pos[1]); z = fma(vel[2], t, pz);
                 r2 = fma(x, x, y * y);
@@ -567,11 +572,18 @@ IMS_DEV bool surf_hit(const ims_surface_t& S, double (&pos)[3], const double (&v
             w = z - p;
             const double k1w = k1 * w;
             const double G = fma(c, fma(k1w, w, r2), -2.0 * w);
-            if (fabs(G) <= 1.0e-8 || it == 5) break;
+            if (PRECISE) {
+                if (converged || it == n_it - 1) break;
+            } else if (fabs(G) <= 1.0e-8 || it == 5) {
+                break;
+            }
             const double s = fma(x, vel[0], y * vel[1]);
             const double wp = fma(-2.0 * dp, s, vel[2]);
             const double Gp = 2.0 * fma(c, fma(k1w, wp, s), -wp);
-            t = t - ddiv(G, Gp);
+            const double dt = ddiv(G, Gp);
+            t = t - dt;
+            // the point is re-evaluated at the final t on the next pass
+            if (PRECISE) converged = !(fabs(dt) > 0x1p-51 * fabs(t));
         }
     }
     const double m = fma(-S.k1c, w, 1.0);
@@ -596,12 +608,13 @@ struct TraceState {
 
 // One surface of the sequential trace: intersect, vignette, reflect or refract.  KIND / SHAPE >= 0: compile-time constants
 // (trace_seq), -1: read from the descriptor.  Returns false when the ray is lost.
-template <int KIND = -1, int SHAPE = -1>
+// PRECISE: surf_hit's Newton to f64 resolution (the optical-path trace).
+template <int KIND = -1, int SHAPE = -1, bool PRECISE = false>
 IMS_DEV bool trace_step(const ims_surface_t& S, TraceState& st, double (&pos)[3], double (&vel)[3], double wave_nm)
 {
     const int kind = (KIND >= 0) ? KIND : S.kind;
     double N[3], nn, r2;
-    if (!surf_hit<SHAPE>(S, pos, vel, N, nn, r2)) return false;
+    if (!surf_hit<SHAPE, PRECISE>(S, pos, vel, N, nn, r2)) return false;
     if (obscured(S, r2)) st.vignetted = 1;
     if (kind == IMS_SURF_BAFFLE || kind == IMS_SURF_DETECTOR) return true;
     if (kind == IMS_SURF_MIRROR) {

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include "ims_photon.h"
 #include "ims_fft.h"
+#include "ims_opd.h"
 
 using namespace ims;
 
@@ -5184,8 +5185,46 @@ int ims_struct_size(int which)
     case 20: return (int)sizeof(ims_plan_input_t);
     case 21: return (int)sizeof(ims_plan_sizes_t);
     case 22: return (int)sizeof(ims_tuning_t);
+    case 23: return (int)sizeof(ims_opd_t);
     }
     return -1;
+}
+
+int ims_opd(const ims_opd_t* P, const ims_optics_t* optics_dev, void* stream)
+{
+    if (!P || !optics_dev) return set_err(IMS_ERR_ARG, "opd / optics is NULL");
+    if (P->n_fields < 0) return set_err(IMS_ERR_ARG, "opd: negative n_fields");
+    if (P->nx < 1 || P->nx > IMS_OPD_MAX_NX) return set_err(IMS_ERR_ARG, "opd: nx out of range");
+    if (P->reference != IMS_OPD_REF_CHIEF && P->reference != IMS_OPD_REF_MEAN) return set_err(IMS_ERR_ARG, "opd: unknown reference");
+    if (P->jmax < 0 || P->jmax > IMS_OPD_MAX_J) return set_err(IMS_ERR_ARG, "opd: jmax out of range (0 .. 66)");
+    if (!(P->dx > 0.0) || !(P->wavelength > 0.0) || !(P->sphere_radius > 0.0))
+        return set_err(IMS_ERR_ARG, "opd: dx, wavelength and sphere_radius must be positive");
+    if (P->n_fields == 0) return IMS_OK;
+    if (!P->dirs || !P->opd || !P->scratch) return set_err(IMS_ERR_ARG, "opd: dirs / opd / scratch is NULL");
+    if (P->jmax > 0) {
+        if (!P->zk_poly || !P->zk_m || !P->zk_ata || !P->zk_atw) return set_err(IMS_ERR_ARG, "opd: Zernike table or output is NULL");
+        if (!(P->r_outer > 0.0) || !(P->eps >= 0.0 && P->eps < 1.0)) return set_err(IMS_ERR_ARG, "opd: r_outer > 0 and 0 <= eps < 1");
+    }
+    const OpdLayout L = opd_layout(*P);
+    if ((L.n_rays + OPD_WG - 1) / OPD_WG > 0x7fffffffLL || L.nblk > 0x7fffffffLL || P->n_fields > 65535)
+        return set_err(IMS_ERR_ARG, "opd: too many rays or fields for one call");
+    hipStream_t s = (hipStream_t)stream;
+    const ims_opd_t A = *P;
+    const dim3 per_block((unsigned)L.nblk, (unsigned)P->n_fields);
+    hipLaunchKernelGGL(k_opd_trace, dim3((unsigned)((L.n_rays + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, optics_dev, L);
+    if (P->reference == IMS_OPD_REF_MEAN) hipLaunchKernelGGL(k_opd_hit_partial, per_block, dim3(OPD_WG), 0, s, A, L);
+    hipLaunchKernelGGL(k_opd_field, dim3((unsigned)P->n_fields), dim3(OPD_WG), 0, s, A, L, 0);
+    hipLaunchKernelGGL(k_opd_sphere, per_block, dim3(OPD_WG), 0, s, A, L);
+    hipLaunchKernelGGL(k_opd_field, dim3((unsigned)P->n_fields), dim3(OPD_WG), 0, s, A, L, 1);
+    const int64_t n_map = (int64_t)P->n_fields * L.npix;
+    hipLaunchKernelGGL(k_opd_map, dim3((unsigned)((n_map + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, L);
+    if (P->jmax > 0) {
+        hipLaunchKernelGGL(k_opd_zk_normal, dim3((unsigned)L.nchunk, (unsigned)P->n_fields), dim3(OPD_WG), 0, s, A, L);
+        const int64_t n_ent = (int64_t)P->n_fields * L.nent;
+        hipLaunchKernelGGL(k_opd_zk_final, dim3((unsigned)((n_ent + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, L);
+    }
+    HIP_TRY(hipGetLastError());
+    return IMS_OK;
 }
 
 int ims_test_math(int which, const double* in_dev, double* out_dev, int64_t n, uint64_t seed, int64_t obj,

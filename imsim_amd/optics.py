@@ -48,6 +48,10 @@ class Telescope:
     pupil_outer: float = 4.18
     pupil_inner: float = 2.558
     name: str = "telescope"
+    # reference-sphere radius [m] of the opd extra output (batoid's sphereRadius); None: none known, opd.compute needs one
+    sphere_radius: Optional[float] = None
+    # annular-Zernike obscuration of the opd extra output (batoid's pupilObscuration); None: pupil_inner / pupil_outer
+    eps: Optional[float] = None
 
     def with_detector_z(self, z):
         surf = [dataclasses.replace(s) for s in self.surfaces]
@@ -164,6 +168,12 @@ def trace_numpy(tel: Telescope, pos, vel, wave_nm):
     return pos, vel, vig, fail
 
 
+# Reference-sphere radius of rubin_like_telescope: its exit-pupil distance, found once by tracing a chief ray (from the stop
+# centre, field 1e-4 rad, r band, refocused detector) and extending it from the detector hit to the optical axis -- the exit
+# pupil of the stand-in is virtual, 2.7038 m beyond the detector (2.7024 .. 2.7062 m over the bands).
+RUBIN_LIKE_SPHERE_RADIUS = 2.7038
+
+
 def rubin_like_telescope(band="r", refocus=True):
     """APPROXIMATE Rubin/LSST prescription (public optical-design values recalled, not batoid's
     LSST_r.yaml): M1/M2/M3, three fused-silica lenses, filter, detector.  The detector position is
@@ -195,7 +205,7 @@ def rubin_like_telescope(band="r", refocus=True):
         Surface(RF, z_l3b, -13.36, 0.0, (), CC, 0.0, 0.361, VACUUM, "L3_exit"),
         Surface(DET, z_det, 0.0, 0.0, (), CC, 0.0, 0.4, name="Detector"),
     ]
-    tel = Telescope(surf, stop_z=0.4393899, in_medium=VACUUM, name=f"rubin_like_{band}")
+    tel = Telescope(surf, stop_z=0.4393899, in_medium=VACUUM, name=f"rubin_like_{band}", sphere_radius=RUBIN_LIKE_SPHERE_RADIUS)
     if refocus:
         tel = refocus_detector(tel)
     return tel
@@ -337,8 +347,10 @@ def load_batoid_yaml(path):
     stop = cfg.get("stopSurface", {})
     stop_z = float((stop.get("coordSys") or {}).get("z", 0.0))
     pupil = float(cfg.get("pupilSize", 8.36)) / 2.0
-    return Telescope(out, stop_z=stop_z, in_medium=in_medium, pupil_outer=pupil,
-                     pupil_inner=pupil * float(cfg.get("pupilObscuration", 0.612)), name=cfg.get("name", "telescope"))
+    eps = float(cfg.get("pupilObscuration", 0.612))
+    sphere = cfg.get("sphereRadius")
+    return Telescope(out, stop_z=stop_z, in_medium=in_medium, pupil_outer=pupil, pupil_inner=pupil * eps,
+                     name=cfg.get("name", "telescope"), sphere_radius=None if sphere is None else float(sphere), eps=eps)
 
 
 # ---------------- ABI struct ----------------

@@ -948,6 +948,47 @@ int  ims_readout_cte(const float* src_dev, float* dst_dev, const ims_readout_t* 
                      int32_t n_band, int32_t axis, void* stream);
 int  ims_readout_finish(const float* seg_dev, const ims_readout_t* ro, uint64_t seed, int32_t* out_dev, void* stream);
 
+/* ---- optical path difference (wavefront) maps: the `opd` extra output (imsim/opd.py) ----
+ * For each field, an nx x nx grid of rays on the entrance pupil (x_i = (i - (nx - 1) / 2) dx, the same for y; pixel (i, j) of
+ * a map is row j, column i) is traced to the detector through the optics descriptor with the optical path length accumulated
+ * (starting phase n_in (d . r), the plane wave's phase from the plane through the origin), closed on the reference sphere
+ * (radius sphere_radius, centred on the chief ray's detector hit or on the mean hit of the unvignetted rays, reached by going
+ * back along each ray) and written as OPD = (t0 - t) * 1e9 nm, NaN where a ray was vignetted or lost.  When jmax > 0 the
+ * per-field normal equations of a least-squares fit of zk_poly / zk_m to the finite pixels are formed as well; the host solves
+ * them.  Every sum runs in a fixed order (per-workgroup partials, then a final pass): the results depend neither on launch
+ * geometry nor on which other fields share the call.  Added in ABI version 22 without changing any existing struct or function
+ * (ims_struct_size 23), so the version number stays. */
+#define IMS_OPD_REF_CHIEF 0
+#define IMS_OPD_REF_MEAN  1
+#define IMS_OPD_MAX_J     66      /* annular Zernikes up to radial order 10 */
+#define IMS_OPD_NPOW      11      /* zk_poly row: coefficients of rho^0 .. rho^10 */
+#define IMS_OPD_MAX_NX    4096
+#define IMS_OPD_BLOCKS(nx) (((int64_t)(nx) * (nx) + 255) / 256)
+#define IMS_OPD_CHUNKS(nx) (((int64_t)(nx) * (nx) + 4095) / 4096)
+#define IMS_OPD_SCRATCH_BYTES(n_fields, nx, jmax) \
+    (8 * (int64_t)(n_fields) * (10 * ((int64_t)(nx) * (nx) + 1) + 6 * IMS_OPD_BLOCKS(nx) + 4 + \
+                                IMS_OPD_CHUNKS(nx) * ((int64_t)(jmax) * ((jmax) + 3) / 2)))
+typedef struct ims_opd {
+    int32_t n_fields;
+    int32_t nx;                   /* 1 .. IMS_OPD_MAX_NX */
+    int32_t reference;            /* IMS_OPD_REF_* */
+    int32_t jmax;                 /* 0 (no fit) .. IMS_OPD_MAX_J */
+    const double* dirs;           /* device [n_fields][3]: unit propagation direction of each field's plane wave (z < 0) */
+    double  dx;                   /* pupil sample spacing [m] */
+    double  wavelength;           /* [nm]: enters through the refractive indices only */
+    double  sphere_radius;        /* [m] */
+    double  r_outer;              /* Zernike outer radius [m] */
+    double  eps;                  /* Zernike inner / outer radius (zk_poly is built for it) */
+    const double* zk_poly;        /* device [jmax][IMS_OPD_NPOW]: radial polynomial of Noll term j in rho = r / r_outer, normalisation included */
+    const int32_t* zk_m;          /* device [jmax]: m > 0 cos(m theta), m < 0 sin(-m theta), 0 radial */
+    double* opd;                  /* device out [n_fields][nx][nx], nm */
+    double* zk_ata;               /* device out [n_fields][jmax (jmax + 1) / 2]: A^T A, upper triangle packed row by row */
+    double* zk_atw;               /* device out [n_fields][jmax]: A^T opd */
+    void*   scratch;              /* device, IMS_OPD_SCRATCH_BYTES(n_fields, nx, jmax) bytes */
+} ims_opd_t;
+/* optics_dev: device ims_optics_t with its derived fields filled (ims_fill_derived_optics) */
+int  ims_opd(const ims_opd_t* opd, const ims_optics_t* optics_dev, void* stream);
+
 /* ---- image helpers ---- */
 int  ims_image_add(double* dst, const double* src, int64_t n, void* stream);
 /* round the f64 accumulation image to the float32 CCD image the reference hands on (galsim.ImageF) */
@@ -965,7 +1006,8 @@ int  ims_enable_timing(int which);
  * which: 0 log, 1 exp, 2 sincos2pi (2 outputs), 3 atan, 4 sincos (2), 5 tanh, 6 gaussian pair of draw(seed,obj,i,slot) (2) */
 /* sizeof() of the ABI structs as compiled, for binding self-checks:
  * 0 object, 1 radial_tables, 2 lin_tables, 3 psf_component, 4 op, 5 surface, 6 tansip, 7 optics, 8 bf_slot,
- * 9 sensor, 10 photons, 11 render_params, 12 plan_item, 13 atmosphere, 14 fft_object, 15 fft_params, 16 readout */
+ * 9 sensor, 10 photons, 11 render_params, 12 plan_item, 13 atmosphere, 14 fft_object, 15 fft_params, 16 readout,
+ * 17 chain, 18 catalog, 19 object_meta, 20 plan_input, 21 plan_sizes, 22 tuning, 23 opd */
 /* Host helpers: fill the derived (uniform) fields of an op / a medium from its primary parameters, so
  * that the kernels do not recompute launch-wide constants per photon.  Call them once when the op
  * chain / the optics descriptor is built; ops and media without derived fields are left untouched. */
