@@ -136,6 +136,32 @@ class Optics(C.Structure):
                 ("rot_g", c_d * 3), ("rot_gnorm", c_d)]
 
 
+IMS_FIG_MAX_DEG = 10
+IMS_FIG_NCOEF = (IMS_FIG_MAX_DEG + 1) * (IMS_FIG_MAX_DEG + 2) // 2
+IMS_LAYOUT_PERTURBED = 0xFFFFFFFFFFFFFFFF
+
+
+def fig_row(p):
+    """IMS_FIG_ROW(p): offset of the coefficients of u^p v^0 .. u^p v^(IMS_FIG_MAX_DEG - p) in ims_surface_frame_t.fig"""
+    return p * (IMS_FIG_MAX_DEG + 1) - p * (p - 1) // 2
+
+
+class SurfaceFrame(C.Structure):
+    """ims_surface_frame_t: the rigid frame and Zernike figure of one surface of a perturbed telescope"""
+    _fields_ = [("moved", c_i32), ("fig_deg", c_i32), ("origin", c_d * 3), ("rot", c_d * 9), ("fig_inv_r", c_d),
+                ("fig", c_d * IMS_FIG_NCOEF)]
+
+
+class Perturbation(C.Structure):
+    _fields_ = [("surf", SurfaceFrame * IMS_MAX_SURFACES)]
+
+
+class OpticsPerturbed(Optics):
+    """ims_optics_perturbed_t: an Optics descriptor followed by its ims_perturbation_t.  A subclass, so that everything that
+    reads an Optics reads this one; the engine launches the perturbed trace (IMS_LAYOUT_PERTURBED) for it."""
+    _fields_ = [("pert", Perturbation)]
+
+
 class BfSlot(C.Structure):
     _fields_ = [("xmin", c_i32), ("ymin", c_i32), ("nx", c_i32), ("ny", c_i32), ("offset", c_i64)]
 
@@ -271,6 +297,8 @@ STRUCTS = [Object, RadialTables, LinTables, PsfComponent, Op, Surface, TanSip, O
 # ims_opd_t is ims_struct_size(23) of the library but not in STRUCTS: the CPU oracle checks its own struct sizes against STRUCTS
 # and has no OPD path, so the one struct only libimsim_hip.so knows is checked by its index alone
 OPD_STRUCT_INDEX = 23
+# ims_optics_perturbed_t and ims_perturbation_t: library-only as well (the oracle traces coaxial telescopes only)
+OPTICS_PERTURBED_STRUCT_INDEX, PERTURBATION_STRUCT_INDEX = 24, 25
 
 # every symbol include/imsim_hip.h declares
 EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_info", "ims_known_optics_layout",
@@ -282,7 +310,7 @@ EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_
            "ims_build_object_table", "ims_patch_stamp_sizes", "ims_gather_rows", "ims_parse_instcat_objects", "ims_screen_prepass",
            "ims_plan_lsst_image", "ims_plan_bind", "ims_plan_upload", "ims_plan_run", "ims_plan_run_deferred", "ims_plans_run_joint", "ims_plan_join", "ims_plan_add_realized", "ims_plan_destroy",
            "ims_fft_inverse", "ims_fft_inverse_raw", "ims_fft_spikes_listed", "ims_fft_warm", "ims_comm_unique_id", "ims_comm_init", "ims_comm_destroy", "ims_reduce_image", "ims_allreduce_delta",
-           "ims_count_inexact", "ims_struct_size", "ims_test_math", "ims_opd"]
+           "ims_count_inexact", "ims_struct_size", "ims_test_math", "ims_opd", "ims_opd_perturbed"]
 
 _LIB_PATH = tuning.env("IMSIM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libimsim_hip.so")
 _lib = None
@@ -381,6 +409,7 @@ def load():
     lib.ims_get_tuning.argtypes = [C.POINTER(Tuning)]
     lib.ims_set_tuning.argtypes = [C.POINTER(Tuning)]
     lib.ims_opd.argtypes = [C.POINTER(Opd), c_vp, c_vp]
+    lib.ims_opd_perturbed.argtypes = [C.POINTER(Opd), c_vp, c_vp]
     _lib = lib
     return lib
 

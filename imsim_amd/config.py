@@ -109,6 +109,13 @@ def load_config(path_or_dict, template_dirs=(), overrides=None):
 
 
 # ---------------- value evaluation ----------------
+# GalSim's angle units: "<value> <unit>" strings evaluate to radians
+ANGLE_UNITS = {"radians": 1.0, "rad": 1.0, "degrees": math.pi / 180.0, "deg": math.pi / 180.0, "hours": math.pi / 12.0,
+               "hour": math.pi / 12.0, "hrs": math.pi / 12.0, "hr": math.pi / 12.0, "h": math.pi / 12.0,
+               "arcminutes": math.pi / 10800.0, "arcmin": math.pi / 10800.0,
+               "arcseconds": math.pi / 648000.0, "arcsec": math.pi / 648000.0}
+
+
 class Evaluator:
     def __init__(self, base):
         self.base = base
@@ -132,9 +139,8 @@ class Evaluator:
             if v.startswith("@"):
                 return self.lookup(v[1:])
             parts = v.split()
-            if len(parts) == 2 and parts[1] in ("degrees", "deg", "radians", "rad"):
-                x = float(parts[0])
-                return math.radians(x) if parts[1].startswith("deg") else x
+            if len(parts) == 2 and parts[1] in ANGLE_UNITS:
+                return float(parts[0]) * ANGLE_UNITS[parts[1]]
             return v
         if isinstance(v, dict) and "type" in v:
             t = v["type"]
@@ -466,6 +472,113 @@ def _process_outputs(out, ev, res, image_dev, det_name, meta, seed):
         res.files.append(fn)
 
 
+# ---------------- input.telescope (imsim/telescope_loader.py) ----------------
+def _angle(v, ev, what):
+    """an Angle value of the config: "<x> <unit>" (GalSim's units), a Degrees / Radians value type or a `$` expression"""
+    if isinstance(v, bool) or isinstance(v, (int, float)):
+        raise GalSimConfigError(f"{what}: an angle needs a unit (e.g. '1 arcmin', '1.e-3 rad'), got {v!r}")
+    x = ev.value(v)
+    if isinstance(x, bool) or not isinstance(x, (int, float)):
+        raise GalSimConfigError(f"{what}: cannot read {v!r} as an angle")
+    return float(x)
+
+
+def parse_perturbations(cfg, ev):
+    """`input.telescope.perturbations` (imsim/telescope_loader.py:286-349) -> the list of dicts optics.apply_perturbations
+    takes: shift as three floats, rotX / rotY / rotZ in rad, Zernike {coef, R_outer, R_inner} (radii None: the optic's)"""
+    if cfg is None or cfg == () or cfg == []:
+        return []
+    groups = cfg if isinstance(cfg, list) else [cfg]
+    out = []
+    for group in groups:
+        if not isinstance(group, dict):
+            raise GalSimConfigError(f"input.telescope.perturbations: expected a dict of optics, got {group!r}")
+        og = {}
+        for optic, perturbs in group.items():
+            if not isinstance(perturbs, dict):
+                raise GalSimConfigError(f"input.telescope.perturbations.{optic}: expected a dict of perturbations")
+            op = {}
+            for ptype, pval in perturbs.items():
+                if ptype == "shift":
+                    xyz = ev.value(pval) if isinstance(pval, (str, dict)) else pval
+                    if not isinstance(xyz, list) or len(xyz) != 3:
+                        raise ValueError("Expecting a list of 3 elements")
+                    vals = []
+                    for x in xyz:
+                        x = ev.value(x)
+                        if isinstance(x, bool) or not isinstance(x, (int, float)):
+                            try:
+                                x = float(x)
+                            except (TypeError, ValueError):
+                                raise ValueError(f"shift of {optic}: cannot read {x!r} as a float") from None
+                        vals.append(float(x))
+                    op["shift"] = vals
+                elif ptype in ("rotX", "rotY", "rotZ"):
+                    op[ptype] = _angle(pval, ev, f"input.telescope.perturbations.{optic}.{ptype}")
+                elif ptype == "Zernike":
+                    if not isinstance(pval, dict):
+                        raise GalSimConfigError(f"input.telescope.perturbations.{optic}.Zernike must be a dict")
+                    r_outer = float(ev.value(pval["R_outer"])) if "R_outer" in pval else None
+                    r_inner = float(ev.value(pval["R_inner"])) if "R_inner" in pval else None
+                    if (r_outer is None) != (r_inner is None):
+                        raise ValueError("Must specify both or neither of R_outer and R_inner")
+                    if "coef" in pval and "idx" in pval:
+                        raise ValueError("Cannot specify both coef and idx for Zernike perturbation")
+                    z = {}
+                    for k in ("coef", "idx", "val"):
+                        if k in pval:
+                            v = ev.value(pval[k])
+                            z[k] = [ev.value(x) for x in v] if isinstance(v, list) else v
+                    op["Zernike"] = {"coef": opticsmod.zernike_coef(z), "R_outer": r_outer, "R_inner": r_inner}
+                else:
+                    raise GalSimConfigError(f"input.telescope.perturbations.{optic}: unknown perturbation {ptype!r} "
+                                            "(shift, rotX, rotY, rotZ, Zernike)")
+            og[optic] = op
+        out.append(og)
+    return out
+
+
+def build_telescope(tel_cfg, ev, band, res=None):
+    """The visit's telescope from `input.telescope`: batoid's YAML file (the approximate Rubin prescription where it is not
+    present), its `perturbations` applied in order, then `focusZ` (a shift of the camera along its axis).  `fea` needs
+    batoid_rubin and is refused."""
+    tel_cfg = tel_cfg or {}
+    if not isinstance(tel_cfg, dict):
+        raise GalSimConfigError("input.telescope must be a dict")
+    if tel_cfg.get("fea"):
+        raise GalSimConfigError("input.telescope.fea (finite-element and active-optics degrees of freedom) needs the batoid_rubin "
+                                "package, which this path does not have; express the perturbation with input.telescope.perturbations "
+                                "(shift, rotX, rotY, rotZ, Zernike) instead")
+    tel_file = ev.value(tel_cfg.get("file_name", "")) if tel_cfg else ""
+    tel = opticsmod.load_batoid_yaml(tel_file) if tel_file and os.path.isfile(tel_file) else opticsmod.rubin_like_telescope(band)
+    if res is not None and not (tel_file and os.path.isfile(tel_file)):
+        note = "input.telescope.file_name (batoid data not present: approximate Rubin prescription)"
+        res.ignored.append(note)
+    perts = parse_perturbations(tel_cfg.get("perturbations"), ev)
+    tel = opticsmod.apply_perturbations(tel, perts)
+    if tel_cfg.get("focusZ") is not None:
+        tel = opticsmod.focus_camera(tel, float(ev.value(tel_cfg["focusZ"])))
+    return tel
+
+
+SAG_KEYS = ("file_name", "nx", "dir")
+
+
+def _process_sag(sag_cfg, ev, out, tel, res):
+    """`output.sag` (imsim/sag.py): one sag map per interface of the visit's telescope"""
+    from . import sag as sagmod
+    if not isinstance(sag_cfg, dict) or "file_name" not in sag_cfg:
+        raise GalSimConfigError("Attribute file_name is required in output.sag")
+    for k in sag_cfg:
+        if k not in SAG_KEYS:
+            raise GalSimConfigError(f"Unexpected attribute {k} found in output.sag")
+    nx = int(ev.value(sag_cfg.get("nx", 255)))
+    fn = os.path.join(str(ev.value(sag_cfg.get("dir", out.get("dir", "")))), str(ev.value(sag_cfg["file_name"])))
+    os.makedirs(os.path.dirname(fn) or ".", exist_ok=True)
+    sagmod.write(fn, sagmod.compute(tel, nx))
+    res.files.append(fn)
+
+
 OPD_REQ = ("file_name", "fields")
 OPD_OPT = ("dir", "rotTelPos", "nx", "wavelength", "projection", "sphereRadius", "reference", "eps", "jmax")
 
@@ -561,7 +674,7 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     out = cfg.get("output", {})
     if out.get("type", "LSST_CCD") not in valid_output_types:
         raise GalSimConfigError(f"Invalid output type {out.get('type')}")
-    for k in ("truth", "photon_pooling_truth", "sag", "process_info", "cosmic_ray_rate"):
+    for k in ("truth", "photon_pooling_truth", "process_info", "cosmic_ray_rate"):
         if k in out:
             res.ignored.append(f"output.{k}")
     ev.vars["det_name"] = None
@@ -581,8 +694,9 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     if itype not in valid_image_types:
         raise GalSimConfigError(f"Invalid image type {itype}")
     if itype == "LSST_Flat":
-        if "opd" in out:                           # a flat has no telescope to trace
-            res.ignored.append("output.opd")
+        for k in ("opd", "sag"):                   # a flat has no telescope to trace
+            if k in out:
+                res.ignored.append(f"output.{k}")
         return _process_flat(cfg, ev, image, res, device, data_dir)
     stamp_cfg = cfg.get("stamp", {})
     stype = stamp_cfg.get("type", "LSST_Silicon")
@@ -596,6 +710,8 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     seed = int(ev.value(image.get("random_seed", meta.get("seed", 0))))
     dets = parallel.shard_ccds(range(first, first + nfiles), rank, world)
     opd_kw = parse_opd(out["opd"], ev) if "opd" in out else None     # config errors before any GPU work
+    tel_cfg = inp.get("telescope", {})
+    build_telescope(tel_cfg, ev, band)                                  # ... the telescope's among them
 
     def prepare(det):
         """Host half of one CCD: scene, catalog, object classification -- everything up to the first GPU call of the CCD
@@ -611,15 +727,11 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
         else:
             nx, ny = builder.setup(img_cfg, det_type_of(det_name))
         # telescope + WCS (input.telescope, image.wcs type Batoid: built by ray tracing, batoid_wcs.py:429-453)
-        tel_cfg = inp.get("telescope", {})
-        tel_file = ev.value(tel_cfg.get("file_name", "")) if tel_cfg else ""
-        tel = opticsmod.load_batoid_yaml(tel_file) if tel_file and os.path.isfile(tel_file) else opticsmod.rubin_like_telescope(band)
-        if not (tel_file and os.path.isfile(tel_file)):
-            res.ignored.append("input.telescope.file_name (batoid data not present: approximate Rubin prescription)")
+        # (perturbations and focusZ included: the photons, the WCS pair and the opd / sag outputs all see the same telescope)
+        tel = build_telescope(tel_cfg, ev, band, res)
         rot_tel = math.radians(meta.get("rotTelPos") or 0.0)
         fp = (100.0, 0.0, (nx - 1) / 2.0 + 0.5, 0.0, 100.0, (ny - 1) / 2.0 + 0.5)
-        optics = _abi.Optics()
-        opticsmod.fill_optics(optics, tel, fp, rot_tel)
+        optics = opticsmod.make_optics(tel, fp, rot_tel)
         ra0, dec0 = math.radians(meta.get("fieldRA") or 0.0), math.radians(meta.get("fieldDec") or 0.0)
         optics.img_wcs, optics.icrf_to_field, _ = opticsmod.build_wcs_pair(
             tel, fp, ra0, dec0, rot_sky=math.radians(meta.get("rotSkyPos") or 0.0), rot_tel_pos=rot_tel, nx=nx, ny=ny)
@@ -837,11 +949,13 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
         res.eimages += sub.eimages
         res.raw += sub.raw
         res.files += sub.files
+    if "sag" in out and rank == 0:
+        # the telescope input of the reference holds the camera turned by the rotator (imsim/telescope_loader.py:242-246)
+        _process_sag(out["sag"], ev, out, opticsmod.with_camera_rotation(build_telescope(tel_cfg, ev, band),
+                                                                         math.radians(meta.get("rotTelPos") or 0.0)), res)
     if opd_kw is not None and rank == 0:
         # the visit's telescope and bandpass, as prepare() builds them
-        tel_cfg = inp.get("telescope", {})
-        tel_file = ev.value(tel_cfg.get("file_name", "")) if tel_cfg else ""
-        tel = opticsmod.load_batoid_yaml(tel_file) if tel_file and os.path.isfile(tel_file) else opticsmod.rubin_like_telescope(band)
+        tel = build_telescope(tel_cfg, ev, band)
         wl, thr = tables.synthetic_r_band()
         _process_opd(out["opd"], opd_kw, ev, out, tel, tables.effective_wavelength(wl, thr), range(first, first + nfiles), res,
                      device)

@@ -71,6 +71,9 @@ IMS_DEV double opd_block_sum(double v, double* lds)
 }
 
 // ray r: pixel p = r mod npix of field r / npix for r < n_fields npix, else the chief ray of field r - n_fields npix
+// PERT: `optics` is an ims_optics_perturbed_t and every surface goes through trace_step_pert (in telescope coordinates
+// throughout: the path lengths and the reference sphere do not depend on the frame they are measured in)
+template <bool PERT = false>
 __global__ __launch_bounds__(256) void k_opd_trace(const ims_opd_t P, const ims_optics_t* __restrict__ optics, OpdLayout L)
 {
     const int64_t r = (int64_t)blockIdx.x * OPD_WG + threadIdx.x;
@@ -104,7 +107,9 @@ __global__ __launch_bounds__(256) void k_opd_trace(const ims_opd_t P, const ims_
         const double p0[3] = { pos[0], pos[1], pos[2] };
         const double v0[3] = { vel[0], vel[1], vel[2] };
         const double n_seg = st.n_cur;               // the medium the ray crosses to reach surface k
-        if (!trace_step<-1, -1, true>(o.surf[k], st, pos, vel, wave)) { status = 2; break; }
+        if (PERT) {
+            if (!trace_step_pert(o.surf[k], perturbation_of(o).surf[k], st, pos, vel, wave, false)) { status = 2; break; }
+        } else if (!trace_step<-1, -1, true>(o.surf[k], st, pos, vel, wave)) { status = 2; break; }
         const double d0 = pos[0] - p0[0], d1 = pos[1] - p0[1], d2 = pos[2] - p0[2];
         double len = sqrt(fma(d0, d0, fma(d1, d1, d2 * d2)));
         if (fma(d0, v0[0], fma(d1, v0[1], d2 * v0[2])) < 0.0) len = -len;     // a surface behind the ray: negative path

@@ -606,17 +606,9 @@ struct TraceState {
     double glass_n, glass_in;
 };
 
-// One surface of the sequential trace: intersect, vignette, reflect or refract.  KIND / SHAPE >= 0: compile-time constants
-// (trace_seq), -1: read from the descriptor.  Returns false when the ray is lost.
-// PRECISE: surf_hit's Newton to f64 resolution (the optical-path trace).
-template <int KIND = -1, int SHAPE = -1, bool PRECISE = false>
-IMS_DEV bool trace_step(const ims_surface_t& S, TraceState& st, double (&pos)[3], double (&vel)[3], double wave_nm)
+// reflect or refract at a hit with normal N (|N|^2 = nn); shared by trace_step and the perturbed trace_step_pert
+IMS_DEV bool bend(const ims_surface_t& S, int kind, TraceState& st, const double (&N)[3], double nn, double (&vel)[3], double wave_nm)
 {
-    const int kind = (KIND >= 0) ? KIND : S.kind;
-    double N[3], nn, r2;
-    if (!surf_hit<SHAPE, PRECISE>(S, pos, vel, N, nn, r2)) return false;
-    if (obscured(S, r2)) st.vignetted = 1;
-    if (kind == IMS_SURF_BAFFLE || kind == IMS_SURF_DETECTOR) return true;
     if (kind == IMS_SURF_MIRROR) {
         // spec v6: (N.N) v - 2 (v.N) N, the reflected direction times |N|^2 -- no division; the length of the velocity
         // carries no information (every later use is homogeneous in it)
@@ -654,6 +646,20 @@ IMS_DEV bool trace_step(const ims_surface_t& S, TraceState& st, double (&pos)[3]
     return true;
 }
 
+// One surface of the sequential trace: intersect, vignette, reflect or refract.  KIND / SHAPE >= 0: compile-time constants
+// (trace_seq), -1: read from the descriptor.  Returns false when the ray is lost.
+// PRECISE: surf_hit's Newton to f64 resolution (the optical-path trace).
+template <int KIND = -1, int SHAPE = -1, bool PRECISE = false>
+IMS_DEV bool trace_step(const ims_surface_t& S, TraceState& st, double (&pos)[3], double (&vel)[3], double wave_nm)
+{
+    const int kind = (KIND >= 0) ? KIND : S.kind;
+    double N[3], nn, r2;
+    if (!surf_hit<SHAPE, PRECISE>(S, pos, vel, N, nn, r2)) return false;
+    if (obscured(S, r2)) st.vignetted = 1;
+    if (kind == IMS_SURF_BAFFLE || kind == IMS_SURF_DETECTOR) return true;
+    return bend(S, kind, st, N, nn, vel, wave_nm);
+}
+
 // An optics LAYOUT is the sequence of (kind, shape) of the surfaces as 4-bit codes, first surface in the lowest nibble:
 // code = 1 + 3 kind_class + shape with kind_class 0 mirror, 1 refracting, 2 detector / baffle; a zero nibble ends the list
 // (at most 15 surfaces).  engine.optics_layout() computes it from the descriptor (ims_render_params_t.optics_layout), and the
@@ -685,8 +691,161 @@ constexpr unsigned long long IMS_LAYOUT_RUBIN_LIKE =
     (3ull << 0) | (3ull << 4) | (3ull << 8) | (5ull << 12) | (5ull << 16) | (4ull << 20) | (6ull << 24) | (5ull << 28) |
     (5ull << 32) | (5ull << 36) | (5ull << 40) | (7ull << 44);
 
+
+// ---------------- perturbed telescopes (include/imsim_hip.h, ims_surface_frame_t) ----------------
+// The figure polynomial and its gradient in the local x, y: Horner in v inside Horner in u, value and both derivatives
+// carried together.
+IMS_DEV void figure_eval(const ims_surface_frame_t& F, double x, double y, double& f, double& fx, double& fy)
+{
+    const double u = x * F.fig_inv_r, v = y * F.fig_inv_r;
+    const int D = F.fig_deg < IMS_FIG_MAX_DEG ? F.fig_deg : IMS_FIG_MAX_DEG;     // never past fig[IMS_FIG_NCOEF - 1]
+    double P = 0.0, Pu = 0.0, Pv = 0.0;
+    for (int p = D; p >= 0; --p) {
+        const double* c = F.fig + IMS_FIG_ROW(p);
+        double a = 0.0, av = 0.0;
+        for (int q = D - p; q >= 0; --q) {
+            av = fma(av, v, a);
+            a = fma(a, v, c[q]);
+        }
+        Pu = fma(Pu, u, P);
+        P = fma(P, u, a);
+        Pv = fma(Pv, u, av);
+    }
+    f = P; fx = Pu * F.fig_inv_r; fy = Pv * F.fig_inv_r;
+}
+
+// surf_hit in the surface's local frame (vertex at the origin) with the figure added to the sag: the same conic root, then
+// Newton on G = c (r2 + k1 w^2) - 2 w with w = z - p(r2) - f(x, y), to f64 resolution of t (the PRECISE stop) whenever the
+// surface has asphere terms or a figure.  The normal of the full sag is (-(g x + m f_x), -(g y + m f_y), m).
+IMS_DEV bool surf_hit_local(const ims_surface_t& S, const ims_surface_frame_t& F, double (&pos)[3], const double (&vel)[3],
+                            double (&N)[3], double& nn, double& r2_out)
+{
+    const bool fig = F.fig_deg > 0;
+    const double pz = pos[2];
+    double t;
+    if (S.R == 0.0 && S.n_asphere == 0 && !fig) {
+        t = ddiv(-pz, vel[2]);
+        pos[0] = fma(vel[0], t, pos[0]); pos[1] = fma(vel[1], t, pos[1]); pos[2] = 0.0;
+        N[0] = 0.0; N[1] = 0.0; N[2] = 1.0; nn = 1.0;
+        r2_out = fma(pos[0], pos[0], pos[1] * pos[1]);
+        return true;
+    }
+    const double c = S.inv_R, k1 = S.k1;
+    if (S.R != 0.0) {
+        const double k1vz = k1 * vel[2];
+        const double A = fma(vel[0], vel[0], fma(vel[1], vel[1], k1vz * vel[2]));
+        const double hb = fma(pos[0], vel[0], fma(pos[1], vel[1], fma(k1vz, pz, -(S.R * vel[2]))));
+        const double C = fma(pos[0], pos[0], fma(pos[1], pos[1], pz * fma(k1, pz, S.m2R)));
+        const double dq = fma(hb, hb, -(A * C));
+        if (dq < 0.0) return false;
+        const double sq = dsqrt0(dq);
+        const double q = -(hb + (hb < 0.0 ? -sq : sq));
+        t = ddiv(C, q);
+    } else {
+        t = ddiv(-pz, vel[2]);
+    }
+    double x = fma(vel[0], t, pos[0]), y = fma(vel[1], t, pos[1]), z = fma(vel[2], t, pz);
+    double r2 = fma(x, x, y * y), w = z, dp = 0.0, fx = 0.0, fy = 0.0;
+    if (S.n_asphere > 0 || fig) {
+        bool converged = false;
+        for (int it = 0; it < 11; ++it) {
+            if (it > 0) {
+                x = fma(vel[0], t, pos[0]); y = fma(vel[1], t, pos[1]); z = fma(vel[2], t, pz);
+                r2 = fma(x, x, y * y);
+            }
+            double p = 0.0, rp = r2;
+            dp = 0.0;
+            for (int k = 0; k < S.n_asphere; ++k) {
+                dp = fma(S.asph_d[k], rp, dp);
+                rp = rp * r2;
+                p = fma(S.asph[k], rp, p);
+            }
+            if (fig) {
+                double f;
+                figure_eval(F, x, y, f, fx, fy);
+                p = p + f;
+            }
+            w = z - p;
+            const double k1w = k1 * w;
+            const double G = fma(c, fma(k1w, w, r2), -2.0 * w);
+            if (converged || it == 10) break;
+            const double s = fma(x, vel[0], y * vel[1]);
+            const double wp = fma(-2.0 * dp, s, vel[2]) - fma(fx, vel[0], fy * vel[1]);
+            const double Gp = 2.0 * fma(c, fma(k1w, wp, s), -wp);
+            const double dt = ddiv(G, Gp);
+            t = t - dt;
+            converged = !(fabs(dt) > 0x1p-51 * fabs(t));
+        }
+    }
+    const double m = fma(-S.k1c, w, 1.0);
+    if (!(m > 0.0)) return false;
+    const double g = fma(2.0 * m, dp, c);
+    pos[0] = x; pos[1] = y; pos[2] = z;
+    N[0] = -fma(g, x, m * fx); N[1] = -fma(g, y, m * fy); N[2] = m;
+    r2_out = r2;
+    nn = fma(N[0], N[0], fma(N[1], N[1], m * m));
+    return true;
+}
+
+// a = R^T (a - o) (into the frame) and back: a = o + R a
+IMS_DEV void frame_in(const ims_surface_frame_t& F, double (&a)[3], bool point)
+{
+    const double* R = F.rot;
+    const double d0 = point ? a[0] - F.origin[0] : a[0];
+    const double d1 = point ? a[1] - F.origin[1] : a[1];
+    const double d2 = point ? a[2] - F.origin[2] : a[2];
+    a[0] = fma(R[0], d0, fma(R[3], d1, R[6] * d2));
+    a[1] = fma(R[1], d0, fma(R[4], d1, R[7] * d2));
+    a[2] = fma(R[2], d0, fma(R[5], d1, R[8] * d2));
+}
+IMS_DEV void frame_out(const ims_surface_frame_t& F, double (&a)[3], bool point)
+{
+    const double* R = F.rot;
+    const double l0 = a[0], l1 = a[1], l2 = a[2];
+    a[0] = fma(R[0], l0, fma(R[1], l1, R[2] * l2));
+    a[1] = fma(R[3], l0, fma(R[4], l1, R[5] * l2));
+    a[2] = fma(R[6], l0, fma(R[7], l1, R[8] * l2));
+    if (point) { a[0] = a[0] + F.origin[0]; a[1] = a[1] + F.origin[1]; a[2] = a[2] + F.origin[2]; }
+}
+
+// One surface of a perturbed telescope.  A surface that is neither moved nor figured is trace_step's PRECISE form (the whole
+// perturbed trace resolves every intersection to f64, so a perturbation does not trade places with the photon path's looser
+// Newton stop); any other goes into its frame, through surf_hit_local and out again -- unless `stay_local` (the detector
+// of the photon trace, whose hit is wanted in the detector's frame).
+IMS_DEV bool trace_step_pert(const ims_surface_t& S, const ims_surface_frame_t& F, TraceState& st, double (&pos)[3],
+                             double (&vel)[3], double wave_nm, bool stay_local)
+{
+    if (!F.moved && F.fig_deg == 0) return trace_step<-1, -1, true>(S, st, pos, vel, wave_nm);
+    if (F.moved) {
+        frame_in(F, pos, true);
+        frame_in(F, vel, false);
+    } else {
+        pos[2] = pos[2] - S.z0;
+    }
+    double N[3], nn, r2;
+    if (!surf_hit_local(S, F, pos, vel, N, nn, r2)) return false;
+    if (obscured(S, r2)) st.vignetted = 1;
+    bool ok = true;
+    if (S.kind != IMS_SURF_BAFFLE && S.kind != IMS_SURF_DETECTOR) ok = bend(S, S.kind, st, N, nn, vel, wave_nm);
+    if (!stay_local) {
+        if (F.moved) {
+            frame_out(F, pos, true);
+            frame_out(F, vel, false);
+        } else {
+            pos[2] = pos[2] + S.z0;
+        }
+    }
+    return ok;
+}
+
+IMS_DEV const ims_perturbation_t& perturbation_of(const ims_optics_t& o)
+{
+    return reinterpret_cast<const ims_optics_perturbed_t*>(&o)->pert;
+}
+
 // returns 0 ok, 1 vignetted, 2 failed.  LAYOUT != 0: the surfaces unrolled for that layout (the host has checked that the
-// descriptor has it), 0: the loop over whatever the descriptor lists.
+// descriptor has it), 0: the loop over whatever the descriptor lists.  IMS_LAYOUT_PERTURBED: the loop of trace_step_pert
+// over an ims_optics_perturbed_t; pos and vel come back in the frame of the last surface (the detector).
 template <unsigned long long LAYOUT = 0ull>
 IMS_DEV int trace(const ims_optics_t& o, double (&pos)[3], double (&vel)[3], double wave_nm)
 {
@@ -695,7 +854,11 @@ IMS_DEV int trace(const ims_optics_t& o, double (&pos)[3], double (&vel)[3], dou
     if (o.in_medium_kind == IMS_MEDIUM_CONST) st.n_cur = o.in_medium_c[0];
     else st.n_cur = medium_n(o.in_medium_kind, o.in_medium_c, wave_nm);
     st.glass_id = -1; st.glass_n = 0.0; st.glass_in = 0.0;
-    if (LAYOUT != 0ull) {
+    if constexpr (LAYOUT == IMS_LAYOUT_PERTURBED) {
+        const ims_perturbation_t& pt = perturbation_of(o);
+        for (int k = 0; k < o.n_surfaces; ++k)
+            if (!trace_step_pert(o.surf[k], pt.surf[k], st, pos, vel, wave_nm, k == o.n_surfaces - 1)) return 2;
+    } else if (LAYOUT != 0ull) {
         if (!TraceSeq<LAYOUT, 0>::run(o, st, pos, vel, wave_nm)) return 2;
     } else {
         for (int k = 0; k < o.n_surfaces; ++k)
@@ -1161,7 +1324,7 @@ IMS_DEV void run_ops(const ims_render_params_t& P, const ims_object_t& o, int64_
         apply_op<IMS_OP_FOCUS_DEPTH>(P, 4, o, k, rng, ph);
         apply_op<IMS_OP_REFRACTION>(P, 5, o, k, rng, ph);
     } else {
-        for (int q = 0; q < P.n_ops; ++q) apply_op(P, q, o, k, rng, ph);
+        for (int q = 0; q < P.n_ops; ++q) apply_op<-1, LAYOUT>(P, q, o, k, rng, ph);
     }
 }
 

@@ -435,6 +435,7 @@ __device__ __forceinline__ void load_photon(const ims_photons_t& pool, int64_t i
 }
 
 // `for op in photon_ops: op.applyTo(photons, ...)` (photon_pooling.py:154-155): one pass, all ops
+template <unsigned long long LAYOUT = 0ull>
 __global__ __launch_bounds__(256) void k_apply_ops(const ims_render_params_t P, const int64_t* __restrict__ photon_offset,
                                                    const ims_photons_t pool)
 {
@@ -447,7 +448,7 @@ __global__ __launch_bounds__(256) void k_apply_ops(const ims_render_params_t P, 
         load_photon(pool, i, ph);
         Rng rng;
         rng_reset(rng);
-        for (int q = 0; q < P.n_ops; ++q) apply_op(P, q, o, k, rng, ph);
+        for (int q = 0; q < P.n_ops; ++q) apply_op<-1, LAYOUT>(P, q, o, k, rng, ph);
         pool.x[i] = ph.x; pool.y[i] = ph.y; pool.flux[i] = ph.flux;
         pool.dxdz[i] = ph.dxdz; pool.dydz[i] = ph.dydz;
         pool.pupil_u[i] = ph.pu; pool.pupil_v[i] = ph.pv; pool.time[i] = ph.t;
@@ -3389,7 +3390,10 @@ int ims_shoot_accumulate(const ims_render_params_t* params_in, void* stream)
         const dim3 grid(grid_for_segments(params->n_segments));
         const int pv = is_default_chain(params) ? psf_variant(params) : -1;
         const bool lay = pv >= 0 && params->optics_layout == IMS_LAYOUT_RUBIN_LIKE && g_tune.layout_kernels != 0;
-        if (pv == 2 && lay) hipLaunchKernelGGL((k_shoot_accumulate<1, 2, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params);
+        // a perturbed telescope (include/imsim_hip.h): the loops over the operators and the surfaces, every surface in its frame
+        if (params->optics_layout == IMS_LAYOUT_PERTURBED)
+            hipLaunchKernelGGL((k_shoot_accumulate<0, 0, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params);
+        else if (pv == 2 && lay) hipLaunchKernelGGL((k_shoot_accumulate<1, 2, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params);
         else if (pv == 2) hipLaunchKernelGGL((k_shoot_accumulate<1, 0>), grid, dim3(256), photon_lds_pad(params), st, *params);
         else if (pv == 1 && lay) hipLaunchKernelGGL((k_shoot_accumulate<1, 1, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params);
         else if (pv == 0 && lay) hipLaunchKernelGGL((k_shoot_accumulate<1, 0, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params);
@@ -3437,7 +3441,12 @@ int ims_shoot_ops_photons(const ims_render_params_t* params, const int64_t* phot
         const dim3 grid(grid_for_segments(params->n_segments));
         const int pv = is_default_chain(params) ? psf_variant(params) : -1;
         const bool lay = pv >= 0 && params->optics_layout == IMS_LAYOUT_RUBIN_LIKE && g_tune.layout_kernels != 0;
-        if (pool->converted && pv == 2 && lay)
+        const bool pert = params->optics_layout == IMS_LAYOUT_PERTURBED;
+        if (pool->converted && pert)
+            hipLaunchKernelGGL((k_shoot_photons<2, 0, 0, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
+        else if (pert)
+            hipLaunchKernelGGL((k_shoot_photons<1, 0, 0, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
+        else if (pool->converted && pv == 2 && lay)
             hipLaunchKernelGGL((k_shoot_photons<2, 1, 2, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
         else if (pool->converted && pv == 2)
             hipLaunchKernelGGL((k_shoot_photons<2, 1, 0>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
@@ -3569,7 +3578,10 @@ int ims_apply_ops(const ims_render_params_t* params, const int64_t* photon_offse
     if (pool->n == 0 || params->n_ops == 0) return IMS_OK;
     hipStream_t st = (hipStream_t)stream;
     {
-        hipLaunchKernelGGL(k_apply_ops, dim3(grid_for_pool(pool->n)), dim3(256), 0, st, *params, photon_offset, *pool);
+        if (params->optics_layout == IMS_LAYOUT_PERTURBED)
+            hipLaunchKernelGGL((k_apply_ops<IMS_LAYOUT_PERTURBED>), dim3(grid_for_pool(pool->n)), dim3(256), 0, st, *params, photon_offset, *pool);
+        else
+            hipLaunchKernelGGL((k_apply_ops<0>), dim3(grid_for_pool(pool->n)), dim3(256), 0, st, *params, photon_offset, *pool);
     }
     HIP_TRY(hipGetLastError());
     return IMS_OK;
@@ -5186,11 +5198,13 @@ int ims_struct_size(int which)
     case 21: return (int)sizeof(ims_plan_sizes_t);
     case 22: return (int)sizeof(ims_tuning_t);
     case 23: return (int)sizeof(ims_opd_t);
+    case 24: return (int)sizeof(ims_optics_perturbed_t);
+    case 25: return (int)sizeof(ims_perturbation_t);
     }
     return -1;
 }
 
-int ims_opd(const ims_opd_t* P, const ims_optics_t* optics_dev, void* stream)
+static int opd_run(const ims_opd_t* P, const ims_optics_t* optics_dev, bool pert, void* stream)
 {
     if (!P || !optics_dev) return set_err(IMS_ERR_ARG, "opd / optics is NULL");
     if (P->n_fields < 0) return set_err(IMS_ERR_ARG, "opd: negative n_fields");
@@ -5211,7 +5225,8 @@ int ims_opd(const ims_opd_t* P, const ims_optics_t* optics_dev, void* stream)
     hipStream_t s = (hipStream_t)stream;
     const ims_opd_t A = *P;
     const dim3 per_block((unsigned)L.nblk, (unsigned)P->n_fields);
-    hipLaunchKernelGGL(k_opd_trace, dim3((unsigned)((L.n_rays + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, optics_dev, L);
+    if (pert) hipLaunchKernelGGL((k_opd_trace<true>), dim3((unsigned)((L.n_rays + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, optics_dev, L);
+    else hipLaunchKernelGGL((k_opd_trace<false>), dim3((unsigned)((L.n_rays + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, optics_dev, L);
     if (P->reference == IMS_OPD_REF_MEAN) hipLaunchKernelGGL(k_opd_hit_partial, per_block, dim3(OPD_WG), 0, s, A, L);
     hipLaunchKernelGGL(k_opd_field, dim3((unsigned)P->n_fields), dim3(OPD_WG), 0, s, A, L, 0);
     hipLaunchKernelGGL(k_opd_sphere, per_block, dim3(OPD_WG), 0, s, A, L);
@@ -5225,6 +5240,16 @@ int ims_opd(const ims_opd_t* P, const ims_optics_t* optics_dev, void* stream)
     }
     HIP_TRY(hipGetLastError());
     return IMS_OK;
+}
+
+int ims_opd(const ims_opd_t* P, const ims_optics_t* optics_dev, void* stream)
+{
+    return opd_run(P, optics_dev, false, stream);
+}
+
+int ims_opd_perturbed(const ims_opd_t* P, const ims_optics_perturbed_t* optics_dev, void* stream)
+{
+    return opd_run(P, optics_dev ? &optics_dev->optics : nullptr, true, stream);
 }
 
 int ims_test_math(int which, const double* in_dev, double* out_dev, int64_t n, uint64_t seed, int64_t obj,

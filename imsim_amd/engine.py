@@ -650,8 +650,15 @@ class BoundScene:
             for k in range(opt.n_surfaces):
                 derive.fill_derived_medium(opt.surf[k].medium_kind, opt.surf[k].medium_c)
             derive.fill_derived_struct("optics", opt)
-            _, P.optics = mem.put_struct(opt)
-            P.optics_layout = optics_layout(opt)
+            if isinstance(opt, _abi.OpticsPerturbed):
+                # a perturbed telescope (include/imsim_hip.h): the descriptor and its frames in one block, the perturbed trace
+                if not isinstance(mem, DeviceMem):
+                    raise ValueError("a perturbed telescope is traced by the library's kernels only (the CPU oracle is coaxial)")
+                _, P.optics = mem.put_struct(opt)
+                P.optics_layout = _abi.IMS_LAYOUT_PERTURBED
+            else:
+                _, P.optics = mem.put_struct(opt)
+                P.optics_layout = optics_layout(opt)
         if scene.atm is not None:
             A = scene.atm.atmosphere_struct()
             scr = scene.atm.screens

@@ -24,6 +24,9 @@ Conventions (batoid is not available here to check its grid against; these are t
   eps R_outer <= r <= R_outer, R_outer = pupil_size / 2), j = 1 .. jmax <= 66, fitted by least squares to the finite
   pixels; AZ_jjj in nm.
 
+A perturbed telescope (optics.apply_perturbations: shifted, rotated or figured surfaces) is traced surface by surface in
+each surface's frame (ims_opd_perturbed); the path lengths and the reference sphere are taken in telescope coordinates.
+
 There is no CPU fallback: without the library or a GPU, compute() raises like the engine does.
 """
 import ctypes as C
@@ -229,7 +232,10 @@ def _run(lib, torch, dev, opt_dev, tel, dirs, nx, dx, wavelength, sphere_radius,
         atw = torch.empty((n, jmax), dtype=torch.float64, device=dev)
         P.zk_ata, P.zk_atw = ata.data_ptr(), atw.data_ptr()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _abi.check(lib.ims_opd(C.byref(P), opt_dev.data_ptr(), stream), "ims_opd")
+    if opt_dev.numel() == C.sizeof(_abi.OpticsPerturbed):
+        _abi.check(lib.ims_opd_perturbed(C.byref(P), opt_dev.data_ptr(), stream), "ims_opd_perturbed")
+    else:
+        _abi.check(lib.ims_opd(C.byref(P), opt_dev.data_ptr(), stream), "ims_opd")
     maps_h = maps.cpu().numpy()
     if jmax == 0:
         return maps_h, None
@@ -267,8 +273,9 @@ def compute(tel, fields, wavelength, nx=255, projection="postel", sphere_radius=
     if not torch.cuda.is_available():
         raise _abi.ImsimHipError("opd.compute needs a GPU (there is no CPU fallback)")
     dev = torch.device(device)
-    opt = _abi.Optics()
-    opticsmod.fill_optics(opt, tel, (1.0, 0.0, 0.0, 0.0, 1.0, 0.0))
+    # a perturbed telescope is traced as the reference's telescope input holds it: with the camera turned by the rotator
+    # (imsim/telescope_loader.py:242-246); for a coaxial one that rotation changes nothing and is left out
+    opt = opticsmod.make_optics(tel, (1.0, 0.0, 0.0, 0.0, 1.0, 0.0), rot_tel_pos if tel.perturbed else 0.0)
     _abi.check(lib.ims_fill_derived_medium(int(opt.in_medium_kind), opt.in_medium_c), "ims_fill_derived_medium")
     for k in range(opt.n_surfaces):
         _abi.check(lib.ims_fill_derived_medium(int(opt.surf[k].medium_kind), opt.surf[k].medium_c), "ims_fill_derived_medium")

@@ -287,6 +287,43 @@ typedef struct ims_optics {
     double  rot_g[3], rot_gnorm;
 } ims_optics_t;
 
+/* ---- perturbed telescopes (input.telescope.perturbations / focusZ, imsim/telescope_loader.py:121-252) ----
+ * A surface that was shifted, rotated or given a Zernike figure carries a rigid frame and an optional figure here.  The
+ * kernels trace it in its LOCAL frame: the ray is moved into the frame, intersected with the surface whose vertex is the
+ * frame's origin (ims_surface_t.z0 is not used for it), vignetted with the local x, y, reflected or refracted with the
+ * normal of the full sag and moved back.  The photon trace hands rubin_op the detector hit in the detector's local frame
+ * (what batoid's trace returns); the camera rotator is then part of the frames and cam_rot must be (1, 0).
+ *
+ * Figure: sag = conic / asphere sag + sum_{p+q <= fig_deg} fig[IMS_FIG_ROW(p) + q] u^p v^q with u = x fig_inv_r,
+ * v = y fig_inv_r -- batoid's Sum([surface, Zernike(coef, R_outer, R_inner)]) with the annular Zernikes expanded once on the
+ * host into this Cartesian polynomial (fig_inv_r = 1 / R_outer).
+ *
+ * How the kernels find it: ims_render_params_t.optics_layout == IMS_LAYOUT_PERTURBED says that `optics` points to an
+ * ims_optics_perturbed_t (the descriptor followed by this block).  That layout runs the surface loop with every surface
+ * intersected to f64 resolution (the Newton of the optical-path trace); the coaxial kernels are not touched by it.  The
+ * opd extra output takes the same block through ims_opd_perturbed.  Sizes: ims_struct_size 24 and 25. */
+#define IMS_FIG_MAX_DEG  10
+#define IMS_FIG_NCOEF    ((IMS_FIG_MAX_DEG + 1) * (IMS_FIG_MAX_DEG + 2) / 2)
+#define IMS_FIG_ROW(p)   ((p) * (IMS_FIG_MAX_DEG + 1) - (p) * ((p) - 1) / 2)   /* row p holds q = 0 .. IMS_FIG_MAX_DEG - p */
+#define IMS_LAYOUT_PERTURBED 0xffffffffffffffffull
+typedef struct ims_surface_frame {
+    int32_t moved;           /* 0: coaxial at (0, 0, z0), no frame transform; 1: origin / rot below */
+    int32_t fig_deg;         /* 0: no figure; 1 .. IMS_FIG_MAX_DEG: degree of the figure polynomial */
+    double  origin[3];       /* vertex of the surface in telescope coordinates [m] */
+    double  rot[9];          /* row-major R: telescope = origin + R local */
+    double  fig_inv_r;       /* 1 / R_outer of the figure */
+    double  fig[IMS_FIG_NCOEF];
+} ims_surface_frame_t;
+
+typedef struct ims_perturbation {
+    ims_surface_frame_t surf[IMS_MAX_SURFACES];   /* one per ims_optics_t.surf */
+} ims_perturbation_t;
+
+typedef struct ims_optics_perturbed {
+    ims_optics_t       optics;
+    ims_perturbation_t pert;
+} ims_optics_perturbed_t;
+
 /* Private pixel-boundary state of one brighter-fatter active region (a bright object's stamp in
  * LSST_Image mode, or the whole CCD in photon-pooling mode). */
 typedef struct ims_bf_slot {
@@ -392,7 +429,8 @@ typedef struct ims_render_params {
      * lowest nibble: code = 1 + 3 kc + shape, kc 0 mirror / 1 refracting / 2 detector or baffle, shape 0 plane / 1 conic
      * (R != 0, no asphere terms) / 2 conic with asphere terms; a zero nibble ends the list.  It MUST describe the descriptor
      * `optics` points to (the kernels cannot check it): for the layouts the library holds an unrolled ray trace for
-     * (ims_known_optics_layout) the launch takes that kernel, any other value runs the loop over the surfaces. */
+     * (ims_known_optics_layout) the launch takes that kernel, any other value runs the loop over the surfaces.
+     * IMS_LAYOUT_PERTURBED: `optics` points to an ims_optics_perturbed_t, traced surface by surface in each surface's frame. */
     uint64_t optics_layout;
     /* optional (NULL = every photon gathers the phase screens itself): the sum over the layers of the screen gradient [nm/m] of
      * every photon, x and y interleaved, filled by ims_screen_prepass and indexed through ims_object_t.screen_base */
@@ -988,6 +1026,8 @@ typedef struct ims_opd {
 } ims_opd_t;
 /* optics_dev: device ims_optics_t with its derived fields filled (ims_fill_derived_optics) */
 int  ims_opd(const ims_opd_t* opd, const ims_optics_t* optics_dev, void* stream);
+/* the same for a perturbed telescope: optics_dev is a device ims_optics_perturbed_t (derived fields filled) */
+int  ims_opd_perturbed(const ims_opd_t* opd, const ims_optics_perturbed_t* optics_dev, void* stream);
 
 /* ---- image helpers ---- */
 int  ims_image_add(double* dst, const double* src, int64_t n, void* stream);
@@ -1007,7 +1047,7 @@ int  ims_enable_timing(int which);
 /* sizeof() of the ABI structs as compiled, for binding self-checks:
  * 0 object, 1 radial_tables, 2 lin_tables, 3 psf_component, 4 op, 5 surface, 6 tansip, 7 optics, 8 bf_slot,
  * 9 sensor, 10 photons, 11 render_params, 12 plan_item, 13 atmosphere, 14 fft_object, 15 fft_params, 16 readout,
- * 17 chain, 18 catalog, 19 object_meta, 20 plan_input, 21 plan_sizes, 22 tuning, 23 opd */
+ * 17 chain, 18 catalog, 19 object_meta, 20 plan_input, 21 plan_sizes, 22 tuning, 23 opd, 24 optics_perturbed, 25 perturbation */
 /* Host helpers: fill the derived (uniform) fields of an op / a medium from its primary parameters, so
  * that the kernels do not recompute launch-wide constants per photon.  Call them once when the op
  * chain / the optics descriptor is built; ops and media without derived fields are left untouched. */
