@@ -300,6 +300,22 @@ OPD_STRUCT_INDEX = 23
 # ims_optics_perturbed_t and ims_perturbation_t: library-only as well (the oracle traces coaxial telescopes only)
 OPTICS_PERTURBED_STRUCT_INDEX, PERTURBATION_STRUCT_INDEX = 24, 25
 
+
+class CrSpan(C.Structure):
+    """ims_cr_span_t: one span of a cosmic-ray footprint (cosmic_rays.CosmicRays.device_tables)"""
+    _fields_ = [("row", c_i32), ("col", c_i32), ("n", c_i32), ("first_pixel", c_i32), ("value_offset", c_i64)]
+
+
+class CrHit(C.Structure):
+    """ims_cr_hit_t: a footprint (or a run of its spans) painted at (x0, y0)"""
+    _fields_ = [("x0", c_i32), ("y0", c_i32), ("first_span", c_i32), ("n_spans", c_i32), ("n_pixels", c_i32), ("pad", c_i32)]
+
+
+CR_SPAN_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("n", "<i4"), ("first_pixel", "<i4"), ("value_offset", "<i8")])
+CR_HIT_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("first_span", "<i4"), ("n_spans", "<i4"), ("n_pixels", "<i4"), ("pad", "<i4")])
+# library-only too (the oracle paints no cosmic rays)
+CR_SPAN_STRUCT_INDEX, CR_HIT_STRUCT_INDEX = 26, 27
+
 # every symbol include/imsim_hip.h declares
 EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_info", "ims_known_optics_layout",
            "ims_tuning_defaults", "ims_get_tuning", "ims_set_tuning", "ims_shoot_accumulate",
@@ -310,7 +326,8 @@ EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_
            "ims_build_object_table", "ims_patch_stamp_sizes", "ims_gather_rows", "ims_parse_instcat_objects", "ims_screen_prepass",
            "ims_plan_lsst_image", "ims_plan_bind", "ims_plan_upload", "ims_plan_run", "ims_plan_run_deferred", "ims_plans_run_joint", "ims_plan_join", "ims_plan_add_realized", "ims_plan_destroy",
            "ims_fft_inverse", "ims_fft_inverse_raw", "ims_fft_spikes_listed", "ims_fft_warm", "ims_comm_unique_id", "ims_comm_init", "ims_comm_destroy", "ims_reduce_image", "ims_allreduce_delta",
-           "ims_count_inexact", "ims_struct_size", "ims_test_math", "ims_opd", "ims_opd_perturbed"]
+           "ims_count_inexact", "ims_struct_size", "ims_test_math", "ims_opd", "ims_opd_perturbed",
+           "ims_paint_cosmic_rays"]
 
 _LIB_PATH = tuning.env("IMSIM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libimsim_hip.so")
 _lib = None
@@ -346,6 +363,9 @@ def load():
             raise ImsimHipError(f"ABI mismatch for {st.__name__}: library {got} bytes, binding {C.sizeof(st)}")
     if lib.ims_struct_size(OPD_STRUCT_INDEX) != C.sizeof(Opd):
         raise ImsimHipError(f"ABI mismatch for Opd: library {lib.ims_struct_size(OPD_STRUCT_INDEX)} bytes, binding {C.sizeof(Opd)}")
+    for k, st, dt in ((CR_SPAN_STRUCT_INDEX, CrSpan, CR_SPAN_DTYPE), (CR_HIT_STRUCT_INDEX, CrHit, CR_HIT_DTYPE)):
+        if not lib.ims_struct_size(k) == C.sizeof(st) == dt.itemsize:
+            raise ImsimHipError(f"ABI mismatch for {st.__name__}: library {lib.ims_struct_size(k)} bytes, binding {C.sizeof(st)}")
     lib.ims_shoot_accumulate.argtypes = [C.POINTER(RenderParams), c_vp]
     lib.ims_shoot_photons.argtypes = [C.POINTER(RenderParams), c_vp, C.POINTER(Photons), c_vp]
     lib.ims_apply_ops.argtypes = [C.POINTER(RenderParams), c_vp, C.POINTER(Photons), c_vp]
@@ -410,6 +430,7 @@ def load():
     lib.ims_set_tuning.argtypes = [C.POINTER(Tuning)]
     lib.ims_opd.argtypes = [C.POINTER(Opd), c_vp, c_vp]
     lib.ims_opd_perturbed.argtypes = [C.POINTER(Opd), c_vp, c_vp]
+    lib.ims_paint_cosmic_rays.argtypes = [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, C.POINTER(c_i64), c_i32, c_vp]
     _lib = lib
     return lib
 

@@ -6,9 +6,10 @@ machinery the four imSim templates exercise for THIS path: template inheritance,
 overrides, `$` (Python eval) and `@` (reference) values, the value types OpsimData / Degrees /
 RADec / Eval / FormattedStr / Sequence / TreeRingCenter / TreeRingFunc, and registries holding the
 same type names (LSST_Silicon, LSST_Photons, LSST_Image, LSST_PhotonPoolingImage, the PhotonOp
-names, AtmosphericPSF / KolmogorovPSF / DoubleGaussianPSF, InstCatObj, ...).  Everything outside
-the path (sky_model, checkpoint, vignetting, readout, truth files, FITS output) is accepted and
-ignored with a note in `Process(...).ignored`.
+names, AtmosphericPSF / KolmogorovPSF / DoubleGaussianPSF, InstCatObj, ...).  The `output` section's
+e-image, readout, truth / photon_pooling_truth / process_info catalogs, cosmic rays, opd and sag are
+produced; what needs data that is not present is accepted and ignored with a note in
+`Process(...).ignored`.
 """
 import copy
 import math
@@ -19,7 +20,7 @@ import numpy as np
 import yaml
 
 from . import _abi, atm_psf, catalog, configs, diffraction, fft_draw, instcat, lsst_image, optics as opticsmod
-from . import flat, opd as opdmod, parallel, readout, sensor as sensormod, tables, treerings, tuning
+from . import cosmic_rays, flat, opd as opdmod, parallel, readout, sensor as sensormod, tables, treerings, truth as truthmod, tuning
 from .engine import Scene, SensorSetup, make_slots
 from .lsst_image import GalSimConfigError
 
@@ -423,12 +424,62 @@ def ccd_seed(seed, det):
     return (x ^ (x >> 31)) >> 2
 
 
+def _exptime(out, ev, meta):
+    return float(ev.value(out.get("exptime", meta.get("exptime") or 30.0)))
+
+
+def parse_catalogs(out, ev, itype):
+    """output.truth / photon_pooling_truth / process_info -> [(key, section)] of those switched on.  The column
+    expressions are tried on an empty CCD here, so that a column that cannot be evaluated fails before any GPU work."""
+    fluxes = ("nominal_flux", "phot_flux", "fft_flux", "incident_flux" if itype == "LSST_PhotonPoolingImage" else "realized_flux")
+    empty = {k: np.zeros(0) for k in ("index", "x", "y") + fluxes}
+    found = []
+    for key in ("truth", "photon_pooling_truth"):
+        c = truthmod.parse(out.get(key), key)
+        if c is None:
+            continue
+        if not c.get("columns"):
+            raise GalSimConfigError(f"Attribute columns is required in output.{key}")
+        truthmod.evaluate_columns(c["columns"], truthmod.object_columns(empty, {"object_id": np.zeros(0, dtype=str)}, None), ev)
+        found.append((key, c))
+    c = truthmod.parse(out.get("process_info"), "process_info", truthmod.PROCESS_INFO_KEYS)
+    if c is not None:
+        truthmod.process_info_columns([])                   # psutil is there
+        found.append(("process_info", c))
+    return found
+
+
+def _write_catalogs(catalogs, ev, out, truth, cat, img_wcs, res):
+    """the catalog files of one CCD (ev holds its variables)"""
+    for key, c in catalogs:
+        if key == "process_info":
+            cols = truthmod.process_info_columns(truth["object_id"])
+        else:
+            cols = truthmod.evaluate_columns(c["columns"], truthmod.object_columns(truth, cat, img_wcs), ev)
+        fn = truthmod.file_name(c, ev, out)
+        truthmod.write(fn, cols)
+        res.files.append(fn)
+
+
+def parse_cosmic_rays(out, ev, data_dir):
+    """output.cosmic_ray_rate [per s per CCD] / cosmic_ray_catalog (imsim/ccd.py:114-136) -> the CosmicRays to paint, or
+    None for a rate of 0"""
+    rate = float(ev.value(out.get("cosmic_ray_rate", 0.0)) or 0.0)
+    if rate < 0.0:
+        raise GalSimConfigError("output.cosmic_ray_rate must be >= 0")
+    if rate == 0.0:
+        return None
+    name = out.get("cosmic_ray_catalog")
+    path = cosmic_rays.find_catalog(str(ev.value(name)) if name not in ("", None) else None, data_dir)
+    return cosmic_rays.CosmicRays(ccd_rate=rate, catalog_file=path)
+
+
 def _process_outputs(out, ev, res, image_dev, det_name, meta, seed):
     """`output` of type LSST_CCD (imsim/ccd.py:92-204) and its `readout` extra output (imsim/readout.py:535-602):
     the e-image gets the header the raw file is built from; with `output.file_name` it is written as FITS; with
     `output.readout` the CCD is read out on the GPU into 16 raw segments (kept in res.raw, written with
     `readout.file_name`)."""
-    exptime = float(ev.value(out.get("exptime", meta.get("exptime") or 30.0)))
+    exptime = _exptime(out, ev, meta)
     camera_name = ev.value(out.get("camera", "LsstCamSim"))
     header_vals = {k: ev.value(v) for k, v in (out.get("header") or {}).items()}
     opsim = {k: v for k, v in meta.items() if v is not None}
@@ -674,9 +725,10 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     out = cfg.get("output", {})
     if out.get("type", "LSST_CCD") not in valid_output_types:
         raise GalSimConfigError(f"Invalid output type {out.get('type')}")
-    for k in ("truth", "photon_pooling_truth", "process_info", "cosmic_ray_rate"):
-        if k in out:
-            res.ignored.append(f"output.{k}")
+    if cfg.get("image", {}).get("type") == "LSST_Flat":
+        for k in ("truth", "photon_pooling_truth", "process_info", "cosmic_ray_rate"):
+            if k in out:
+                res.ignored.append(f"output.{k}")
     ev.vars["det_name"] = None
     ev.vars["camera_info"] = camera_info(str(ev.value(out.get("camera", "LsstCamSim"))), data_dir)
     ev.load_eval_variables({k: v for k, v in cfg.get("eval_variables", {}).items() if k not in ("dcamera_info",)})
@@ -710,6 +762,8 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     seed = int(ev.value(image.get("random_seed", meta.get("seed", 0))))
     dets = parallel.shard_ccds(range(first, first + nfiles), rank, world)
     opd_kw = parse_opd(out["opd"], ev) if "opd" in out else None     # config errors before any GPU work
+    catalogs = parse_catalogs(out, ev, itype)
+    crs = parse_cosmic_rays(out, ev, data_dir)
     tel_cfg = inp.get("telescope", {})
     build_telescope(tel_cfg, ev, band)                                  # ... the telescope's among them
 
@@ -854,7 +908,7 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
                                         "on this path (imsim/stamp.py:493-499).  Remove the key (as config/imsim-config.yaml does) or force "
                                         "stamp.draw_method: phot")
         ctx = types.SimpleNamespace(det=det, det_name=det_name, scene=scene, builder=builder, truth=truth, seed_ccd=seed_ccd,
-                                    nx=nx, ny=ny, job=None, pooling=None)
+                                    nx=nx, ny=ny, job=None, pooling=None, cat=cat)
         if itype == "LSST_PhotonPoolingImage":
             ctx.pooling = dict(cat=cat, phot_flux=phot, make_objects=make_objects, max_flux_simple=max_simple, seed=seed_ccd, truth=truth,
                                fft_sb_thresh=float(ev.value(stamp_cfg.get("fft_sb_thresh", 0.0))), kpsf=kpsf, fwhm_total=fwhm_total,
@@ -899,15 +953,20 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     done = {}
 
     def finish(ctx, renderer):
-        """One CCD's image is through: truth record, host copy, `output` (e-image, readout) from the device image."""
+        """One CCD's image is through: truth record, cosmic rays, host copy, `output` (e-image, readout, catalogs) from the
+        device image."""
         ev.vars["det_name"] = ctx.det_name                   # `output.file_name` and friends are evaluated per CCD
         ev.vars["_sequence_index"] = ctx.det
         renderer.synchronize()
         if ctx.job is not None:
             lsst_image.fill_truth(ctx.truth, ctx.job, ctx.job.realized.cpu().numpy())
+        ctx.truth["object_id"] = np.asarray(ctx.cat["object_id"])[np.asarray(ctx.truth["index"], dtype=np.int64)]
+        if crs is not None:                                  # on the e-image, before the readout (imsim/ccd.py:122-136)
+            crs.paint_hip(renderer.image, cosmic_rays.ccd_rng(ctx.seed_ccd), exptime=_exptime(out, ev, meta))
         sub = ProcessResult()
         img = renderer.image_numpy()                         # the e-image as rendered: the readout chain bleeds the device image in place
         _process_outputs(out, ev, sub, renderer.image, ctx.det_name, meta, ctx.seed_ccd)
+        _write_catalogs(catalogs, ev, out, ctx.truth, ctx.cat, ctx.scene.optics.img_wcs, sub)
         done[ctx.det] = (img, ctx.truth, ctx.det_name, sub)
 
     # Several CCDs of LSST_Image type go through the overlapped focal-plane path (focal_plane.render_focal_plane, the per-CCD

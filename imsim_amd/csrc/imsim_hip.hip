@@ -2195,6 +2195,33 @@ __global__ __launch_bounds__(256) void k_image_to_float(const double* __restrict
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = (float)src[i];
 }
 
+// One workgroup per hit of a layer, a lane per span pixel.  The hits of a layer cover disjoint pixels (the caller's layering),
+// so the plain read-add-write below has no races, and each pixel sees its adds in layer order.  A footprint has some tens of
+// pixels: one wave per hit, the span of a pixel by binary search over the footprint's pixel prefix.
+__global__ __launch_bounds__(64) void k_paint_cosmic_rays(double* __restrict__ image, int32_t nx, int32_t ny,
+                                                          const ims_cr_span_t* __restrict__ spans, int64_t n_spans,
+                                                          const double* __restrict__ values, int64_t n_values,
+                                                          const ims_cr_hit_t* __restrict__ hits)
+{
+    const ims_cr_hit_t h = hits[blockIdx.x];
+    if (h.n_spans < 1 || h.first_span < 0 || (int64_t)h.first_span + h.n_spans > n_spans) return;
+    const int32_t base = spans[h.first_span].first_pixel;
+    for (int32_t k = threadIdx.x; k < h.n_pixels; k += blockDim.x) {
+        int32_t lo = h.first_span, hi = h.first_span + h.n_spans - 1;        // last span whose first pixel is <= k
+        while (lo < hi) {
+            const int32_t mid = lo + (hi - lo + 1) / 2;
+            if (spans[mid].first_pixel - base <= k) lo = mid;
+            else hi = mid - 1;
+        }
+        const ims_cr_span_t s = spans[lo];
+        const int32_t dx = k - (s.first_pixel - base);
+        if (dx < 0 || dx >= s.n || s.value_offset < 0 || s.value_offset + dx >= n_values) continue;
+        const int64_t row = (int64_t)h.y0 + s.row, col = (int64_t)h.x0 + s.col + dx;
+        if (row < 0 || row >= ny || col < 0 || col >= nx) continue;
+        image[row * nx + col] += values[s.value_offset + dx];
+    }
+}
+
 
 // ---------------- FFT branch ----------------
 __device__ __forceinline__ int64_t find_prefix(const int64_t* __restrict__ prefix, int64_t n, int64_t e)
@@ -4797,6 +4824,30 @@ int ims_image_add(double* dst, const double* src, int64_t n, void* stream)
     return IMS_OK;
 }
 
+int ims_paint_cosmic_rays(double* image_dev, int32_t nx, int32_t ny, const ims_cr_span_t* spans_dev, int64_t n_spans,
+                          const double* values_dev, int64_t n_values, const ims_cr_hit_t* hits_dev, const int64_t* layer_first,
+                          int32_t n_layers, void* stream)
+{
+    if (n_layers < 0 || (n_layers > 0 && !layer_first)) return set_err(IMS_ERR_ARG, "cosmic rays: bad layer list");
+    if (n_layers == 0 || layer_first[n_layers] == 0) return IMS_OK;
+    if (!image_dev || !spans_dev || !values_dev || !hits_dev) return set_err(IMS_ERR_ARG, "cosmic rays: image / spans / values / hits is NULL");
+    if (nx < 1 || ny < 1 || n_spans < 1 || n_spans > 0x7fffffffLL || n_values < 1)
+        return set_err(IMS_ERR_ARG, "cosmic rays: empty image or catalog");
+    if (layer_first[0] != 0) return set_err(IMS_ERR_ARG, "cosmic rays: layer_first[0] must be 0");
+    for (int32_t l = 0; l < n_layers; ++l)
+        if (layer_first[l + 1] < layer_first[l] || layer_first[l + 1] - layer_first[l] > 0x7fffffffLL)
+            return set_err(IMS_ERR_ARG, "cosmic rays: layer_first must be non-decreasing");
+    hipStream_t st = (hipStream_t)stream;
+    for (int32_t l = 0; l < n_layers; ++l) {
+        const int64_t n = layer_first[l + 1] - layer_first[l];
+        if (n == 0) continue;
+        hipLaunchKernelGGL(k_paint_cosmic_rays, dim3((unsigned)n), dim3(64), 0, st, image_dev, nx, ny, spans_dev, n_spans, values_dev,
+                           n_values, hits_dev + layer_first[l]);
+    }
+    HIP_TRY(hipGetLastError());
+    return IMS_OK;
+}
+
 // Launch-wide constants of the air index (host arithmetic, IEEE binary64, same operation order as the
 // oracle's restatement): n - 1 = air_p * dispersion(wavelength) - air_w * water(wavelength).
 static void air_factors(double p_kpa, double t_k, double h2o_kpa, double* air_p, double* air_w)
@@ -5200,6 +5251,8 @@ int ims_struct_size(int which)
     case 23: return (int)sizeof(ims_opd_t);
     case 24: return (int)sizeof(ims_optics_perturbed_t);
     case 25: return (int)sizeof(ims_perturbation_t);
+    case 26: return (int)sizeof(ims_cr_span_t);
+    case 27: return (int)sizeof(ims_cr_hit_t);
     }
     return -1;
 }

@@ -231,8 +231,9 @@ def make_carriers(gs, gscfg):
             readout.EImage(data[0].array, hdr).write(file_name)
 
     class CarryExtraOutput(gscfg.ExtraOutputBuilder):
-        """readout / photon_pooling_truth / opd / sag / process_info: accepted; the e-image -> raw-file chain of this package
-        runs from imsim_amd.config.Process (`output.readout`), not from GalSim's extra-output hooks"""
+        """readout / photon_pooling_truth / opd / sag / process_info: accepted here; the files are written by
+        imsim_amd.config.Process, which the image builder runs with the config's `output` section (readout, truth catalogs,
+        process info, cosmic rays, opd, sag), not from GalSim's extra-output hooks"""
 
         def initialize(self, data, scratch, config, base, logger):
             self.data, self.scratch = data, scratch

@@ -1029,6 +1029,30 @@ int  ims_opd(const ims_opd_t* opd, const ims_optics_t* optics_dev, void* stream)
 /* the same for a perturbed telescope: optics_dev is a device ims_optics_perturbed_t (derived fields filled) */
 int  ims_opd_perturbed(const ims_opd_t* opd, const ims_optics_perturbed_t* optics_dev, void* stream);
 
+/* ---- cosmic rays on the e-image (imsim/cosmic_rays.py:paint_cr) ----
+ * A footprint of the catalog is a run of spans; a hit paints one footprint (or a run of its spans) at (x0, y0).  Every span
+ * pixel lands on image[y0 + row][x0 + col + k] += values[value_offset + k] (k = 0 .. n-1); pixels off the image are dropped.
+ * The hits are given in layers, hits_dev[layer_first[l] .. layer_first[l+1]): the hits of one layer cover disjoint pixels,
+ * and layer l is added before layer l+1 -- so every pixel receives its adds in the order the caller laid out (the draw order
+ * of the reference), whatever the image values, and the result is bitwise reproducible. */
+typedef struct ims_cr_span {
+    int32_t row, col;             /* offset of the span's first pixel from the hit's (x0, y0) */
+    int32_t n;                    /* pixels in the span */
+    int32_t first_pixel;          /* pixels of the footprint's spans before this one (non-decreasing along a footprint) */
+    int64_t value_offset;         /* index of the span's first value in values_dev */
+} ims_cr_span_t;
+typedef struct ims_cr_hit {
+    int32_t x0, y0;               /* destination of the footprint's origin, image pixels (0-based) */
+    int32_t first_span, n_spans;  /* spans_dev[first_span .. first_span + n_spans) */
+    int32_t n_pixels;             /* sum of their n */
+    int32_t pad;
+} ims_cr_hit_t;
+/* image_dev: device f64 [ny][nx]; spans_dev [n_spans], values_dev [n_values]: device tables of the catalog; hits_dev: device
+ * [layer_first[n_layers]]; layer_first: HOST [n_layers + 1], non-decreasing from 0 */
+int  ims_paint_cosmic_rays(double* image_dev, int32_t nx, int32_t ny, const ims_cr_span_t* spans_dev, int64_t n_spans,
+                           const double* values_dev, int64_t n_values, const ims_cr_hit_t* hits_dev, const int64_t* layer_first,
+                           int32_t n_layers, void* stream);
+
 /* ---- image helpers ---- */
 int  ims_image_add(double* dst, const double* src, int64_t n, void* stream);
 /* round the f64 accumulation image to the float32 CCD image the reference hands on (galsim.ImageF) */
@@ -1047,7 +1071,8 @@ int  ims_enable_timing(int which);
 /* sizeof() of the ABI structs as compiled, for binding self-checks:
  * 0 object, 1 radial_tables, 2 lin_tables, 3 psf_component, 4 op, 5 surface, 6 tansip, 7 optics, 8 bf_slot,
  * 9 sensor, 10 photons, 11 render_params, 12 plan_item, 13 atmosphere, 14 fft_object, 15 fft_params, 16 readout,
- * 17 chain, 18 catalog, 19 object_meta, 20 plan_input, 21 plan_sizes, 22 tuning, 23 opd, 24 optics_perturbed, 25 perturbation */
+ * 17 chain, 18 catalog, 19 object_meta, 20 plan_input, 21 plan_sizes, 22 tuning, 23 opd, 24 optics_perturbed, 25 perturbation,
+ * 26 cr_span, 27 cr_hit */
 /* Host helpers: fill the derived (uniform) fields of an op / a medium from its primary parameters, so
  * that the kernels do not recompute launch-wide constants per photon.  Call them once when the op
  * chain / the optics descriptor is built; ops and media without derived fields are left untouched. */
