@@ -11,7 +11,7 @@ import numpy as np
 from . import tuning
 
 IMS_OBJ_FAINT = 1
-IMS_PSF_GAUSSIAN, IMS_PSF_RADIAL, IMS_PSF_SCREENS, IMS_PSF_DOUBLE_GAUSSIAN = 1, 2, 3, 4
+IMS_PSF_GAUSSIAN, IMS_PSF_RADIAL, IMS_PSF_SCREENS, IMS_PSF_DOUBLE_GAUSSIAN, IMS_PSF_OPTICAL_SCREEN = 1, 2, 3, 4, 5
 IMS_MAX_LAYERS = 8
 IMS_MAX_PSF = 4
 (IMS_OP_TIME_SAMPLER, IMS_OP_PUPIL_ANNULUS_SAMPLER, IMS_OP_PHOTON_DCR, IMS_OP_RUBIN_OPTICS,
@@ -77,6 +77,21 @@ class Atmosphere(C.Structure):
                 ("screens", c_vp),
                 ("dn", c_d), ("inv_n", c_d), ("inv_scale", c_d), ("aper_ri2", c_d), ("aper_dr2", c_d),
                 ("screen_quads", c_vp)]
+
+
+IMS_OPT_NZ, IMS_OPT_NFIELD, IMS_OPT_NPUPIL = 19, 15, 28
+
+
+class OpticalScreen(C.Structure):
+    """ims_optical_screen_t: the optical phase screen of AtmosphericPSF(doOpt=True) (optical_system.OpticalZernikes.screen_struct)"""
+    _fields_ = [("field", (c_d * IMS_OPT_NFIELD) * IMS_OPT_NZ), ("pupil", (c_d * IMS_OPT_NPUPIL) * IMS_OPT_NZ),
+                ("r_outer", c_d), ("remap", c_d), ("lam0", c_d), ("inv_r", c_d), ("grad_scale", c_d)]
+
+
+class AtmosphereOptical(Atmosphere):
+    """ims_atmosphere_optical_t: an Atmosphere descriptor followed by the optical screen.  A subclass, so that everything that
+    reads an Atmosphere reads this one; a PSF list with IMS_PSF_OPTICAL_SCREEN needs `atm` to point to one."""
+    _fields_ = [("opt", OpticalScreen)]
 
 
 class KPsf(C.Structure):
@@ -315,6 +330,8 @@ CR_SPAN_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("n", "<i4"), ("first_
 CR_HIT_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("first_span", "<i4"), ("n_spans", "<i4"), ("n_pixels", "<i4"), ("pad", "<i4")])
 # library-only too (the oracle paints no cosmic rays)
 CR_SPAN_STRUCT_INDEX, CR_HIT_STRUCT_INDEX = 26, 27
+# and the optical phase screen (the oracle has no such component)
+OPTICAL_SCREEN_STRUCT_INDEX, ATMOSPHERE_OPTICAL_STRUCT_INDEX = 28, 29
 
 # every symbol include/imsim_hip.h declares
 EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_info", "ims_known_optics_layout",
@@ -327,7 +344,7 @@ EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_
            "ims_plan_lsst_image", "ims_plan_bind", "ims_plan_upload", "ims_plan_run", "ims_plan_run_deferred", "ims_plans_run_joint", "ims_plan_join", "ims_plan_add_realized", "ims_plan_destroy",
            "ims_fft_inverse", "ims_fft_inverse_raw", "ims_fft_spikes_listed", "ims_fft_warm", "ims_comm_unique_id", "ims_comm_init", "ims_comm_destroy", "ims_reduce_image", "ims_allreduce_delta",
            "ims_count_inexact", "ims_struct_size", "ims_test_math", "ims_opd", "ims_opd_perturbed",
-           "ims_paint_cosmic_rays"]
+           "ims_paint_cosmic_rays", "ims_test_optical_screen"]
 
 _LIB_PATH = tuning.env("IMSIM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libimsim_hip.so")
 _lib = None
@@ -365,6 +382,9 @@ def load():
         raise ImsimHipError(f"ABI mismatch for Opd: library {lib.ims_struct_size(OPD_STRUCT_INDEX)} bytes, binding {C.sizeof(Opd)}")
     for k, st, dt in ((CR_SPAN_STRUCT_INDEX, CrSpan, CR_SPAN_DTYPE), (CR_HIT_STRUCT_INDEX, CrHit, CR_HIT_DTYPE)):
         if not lib.ims_struct_size(k) == C.sizeof(st) == dt.itemsize:
+            raise ImsimHipError(f"ABI mismatch for {st.__name__}: library {lib.ims_struct_size(k)} bytes, binding {C.sizeof(st)}")
+    for k, st in ((OPTICAL_SCREEN_STRUCT_INDEX, OpticalScreen), (ATMOSPHERE_OPTICAL_STRUCT_INDEX, AtmosphereOptical)):
+        if lib.ims_struct_size(k) != C.sizeof(st):
             raise ImsimHipError(f"ABI mismatch for {st.__name__}: library {lib.ims_struct_size(k)} bytes, binding {C.sizeof(st)}")
     lib.ims_shoot_accumulate.argtypes = [C.POINTER(RenderParams), c_vp]
     lib.ims_shoot_photons.argtypes = [C.POINTER(RenderParams), c_vp, C.POINTER(Photons), c_vp]
@@ -406,6 +426,7 @@ def load():
     lib.ims_readout_cte.argtypes = [c_vp, c_vp, C.POINTER(Readout), c_vp, c_i32, c_i32, c_vp]
     lib.ims_readout_finish.argtypes = [c_vp, C.POINTER(Readout), c_u64, c_vp, c_vp]
     lib.ims_test_math.argtypes = [C.c_int, c_vp, c_vp, c_i64, c_u64, c_i64, C.c_uint32, c_vp]
+    lib.ims_test_optical_screen.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]
     lib.ims_plan_lsst_image.argtypes = [C.POINTER(PlanInput), C.POINTER(c_vp), C.POINTER(PlanSizes)]
     lib.ims_plan_bind.argtypes = [c_vp, C.POINTER(RenderParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.ims_plan_upload.argtypes = [c_vp, c_vp]

@@ -18,7 +18,7 @@ import numpy as np
 from scipy import special
 from scipy.optimize import bisect
 
-from . import _abi, tables
+from . import _abi, optical_system, tables
 
 ARCSEC = 180.0 / math.pi * 3600.0
 WLEN_EFF = dict(u=365.49, g=480.03, r=622.20, i=754.06, z=868.21, y=991.66)   # atmPSF.py:125
@@ -125,10 +125,16 @@ def second_kick_table(lam, r0, diam, obscuration, kcrit, n_bins=tables.N_BINS, t
 class AtmosphericPSF:
     """Mirror of imsim.atmPSF.AtmosphericPSF: same constructor arguments and derived quantities
     (targetFWHM :128, six layers with Ellerbroek altitudes/weights, truncated log-normal L0,
-    r0_500 solved for the target seeing, speeds <= 20 m/s, isotropic directions :244-296)."""
+    r0_500 solved for the target seeing, speeds <= 20 m/s, isotropic directions :244-296).
+
+    doOpt (:204-205, OptWF :37-76): one more phase screen, the residual aberrations of the optics -- an
+    optical_system.OpticalZernikes drawn once per visit from a generator of its own (optical_system.visit_optical_state), whose
+    tables are read from <data_dir>/optics_data/.  optical_deviations: the 50 deviations as given instead of drawn ones;
+    optical_nominal=False leaves the design's nominal coefficients out (tests set known states with the two)."""
 
     def __init__(self, airmass, rawSeeing, band, boresight=None, seed=0, t0=0.0, exptime=30.0, kcrit=0.2,
-                 screen_size=819.2, screen_scale=0.1, exponent=-0.3, no2k=False, device=None):
+                 screen_size=819.2, screen_scale=0.1, exponent=-0.3, no2k=False, device=None, doOpt=False, data_dir=None,
+                 optical_deviations=None, optical_nominal=True):
         self.airmass, self.rawSeeing, self.boresight = airmass, rawSeeing, boresight
         self.wlen_eff = WLEN_EFF[band]
         self.targetFWHM = rawSeeing * airmass ** 0.6 * (self.wlen_eff / 500.0) ** (-0.3)
@@ -144,6 +150,10 @@ class AtmosphericPSF:
         self.kmax = kcrit / self.r0
         self.screens = self._build_screens(rng, device)
         self.second_kick = None if no2k else second_kick_table(self.wlen_eff, self.r0, self.diam, self.obscuration, kcrit)
+        # after everything the atmosphere's stream is drawn for, and from another generator: the atmosphere does not depend on doOpt
+        self.doOpt = bool(doOpt)
+        self.opt = (optical_system.visit_optical_state(seed, data_dir, deviations=optical_deviations, nominal=optical_nominal)
+                    if self.doOpt else None)
 
     def _get_atm_kwargs(self, rng):
         altitudes = [0.2, 2.58, 5.16, 7.73, 12.89, 15.46]                         # km, ground layer raised (:249-252)
@@ -177,7 +187,9 @@ class AtmosphericPSF:
     # -- what the kernels consume --
     def atmosphere_struct(self):
         """_abi.Atmosphere without the screens pointer (filled when bound to a memory provider)."""
-        A = _abi.Atmosphere()
+        A = _abi.Atmosphere() if self.opt is None else _abi.AtmosphereOptical()
+        if self.opt is not None:
+            A.opt = self.opt.screen_struct()
         A.n_layers, A.npix, A.scale = len(self.altitudes), self.npix, self.screen_scale
         A.x0 = -0.5 * self.npix * self.screen_scale
         A.t0, A.exptime = self.t0, self.exptime
@@ -190,8 +202,15 @@ class AtmosphericPSF:
 
     def psf_components(self, second_kick_table_id):
         """PSF component tuples for Scene.psf: ChromaticAtmosphere(PhaseScreenPSF, alpha=exponent,
-        base_wavelength=wlen_eff) then the achromatic second kick (atmPSF.py:305-322)."""
+        base_wavelength=wlen_eff), the achromatic second kick, then with doOpt the achromatic optical screen (atmPSF.py:305-334)."""
         comps = [(_abi.IMS_PSF_SCREENS, 0, 1.0e-9 * ARCSEC, self.exponent, self.wlen_eff)]
         if self.second_kick is not None:
             comps.append((_abi.IMS_PSF_RADIAL, second_kick_table_id, 1.0, 0.0, 1.0))
+        if self.opt is not None:
+            comps.append(self.optical_component())
         return comps
+
+    @staticmethod
+    def optical_component():
+        """the optical screen's component: the screens' unit conversion (nm per m -> radians -> arcsec), no wavelength dependence"""
+        return (_abi.IMS_PSF_OPTICAL_SCREEN, 0, 1.0e-9 * ARCSEC, 0.0, 1.0)

@@ -19,7 +19,7 @@ import types
 import numpy as np
 import yaml
 
-from . import _abi, atm_psf, catalog, configs, diffraction, fft_draw, instcat, lsst_image, optics as opticsmod
+from . import _abi, atm_psf, catalog, configs, diffraction, fft_draw, instcat, lsst_image, optical_system, optics as opticsmod
 from . import cosmic_rays, flat, opd as opdmod, parallel, readout, sensor as sensormod, tables, treerings, truth as truthmod, tuning
 from .engine import Scene, SensorSetup, make_slots
 from .lsst_image import GalSimConfigError
@@ -461,6 +461,50 @@ def _write_catalogs(catalogs, ev, out, truth, cat, img_wcs, res):
         res.files.append(fn)
 
 
+def parse_atm_psf_options(atm_cfg, stamp_cfg, ev, data_dir, res, itype="LSST_Image", psf_cfg=None):
+    """What input.atm_psf's doOpt and save_file ask for, checked before any GPU work.  doOpt (the optical phase screen,
+    atm_psf.AtmosphericPSF) needs the three tables of <data_dir>/optics_data/, room for one more PSF component and a render in
+    which no object can take the FFT branch; save_file has no effect and is reported.  Returns doOpt.
+
+    FFT branch in reach: LSST_Image draws by FFT when stamp.fft_sb_thresh is set and stamp.draw_method is not `phot`, and
+    everything with draw_method `fft` (lsst_image.prepare honours draw_method); LSST_PhotonPoolingImage decides from fft_sb_thresh alone (as the reference's
+    photon pooling does: its FFT batch does not look at draw_method), so there only the absence of the threshold rules it out."""
+    if not atm_cfg:
+        return False
+    if "save_file" in atm_cfg:
+        # a pickle of the GalSim atmosphere, for GalSim to read back: no such objects exist here
+        note = "input.atm_psf.save_file (the atmosphere is regenerated from the visit seed; no GalSim pickle is written)"
+        if note not in res.ignored:
+            res.ignored.append(note)
+    if not bool(ev.value(atm_cfg.get("doOpt", False))):
+        return False
+    pooling = itype == "LSST_PhotonPoolingImage"
+    thresh = float(ev.value(stamp_cfg.get("fft_sb_thresh", 0.0)))
+    method = str(ev.value(stamp_cfg.get("draw_method", "auto")))
+    if (thresh and (pooling or method != "phot")) or (method == "fft" and not pooling):
+        # an object CAN take the FFT branch, where the reference swaps the optical screen for galsim.OpticalPSF
+        # (imsim/psf_utils.py:126-145): a per-object, non-radial MTF that the FFT branch here does not hold.  Never a silently
+        # different image.
+        way_out = ("Remove stamp.fft_sb_thresh (image.type LSST_PhotonPoolingImage sends objects above it to the FFT branch whatever "
+                   "stamp.draw_method says)" if pooling else "Force stamp.draw_method: phot (or remove stamp.fft_sb_thresh)")
+        raise GalSimConfigError("input.atm_psf.doOpt with the FFT branch in reach is not supported: FFT-drawn objects would need "
+                                "galsim.OpticalPSF (imsim/psf_utils.py:126-145), which is not built on this path.  " + way_out)
+    if psf_cfg is not None:
+        # the screens, the second kick and the optical screen are three of the IMS_MAX_PSF components of a launch
+        items = psf_cfg["items"] if psf_cfg.get("type") == "Convolve" else [psf_cfg]
+        others = sum(2 if it.get("type") == "KolmogorovPSF" else 1 for it in items if it.get("type") != "AtmosphericPSF")
+        n_atm = 3 - (1 if bool(ev.value(atm_cfg.get("_no2k", False))) else 0)
+        if any(it.get("type") == "AtmosphericPSF" for it in items) and n_atm + others > _abi.IMS_MAX_PSF:
+            raise GalSimConfigError(f"input.atm_psf.doOpt: the psf would have {n_atm + others} components (AtmosphericPSF with the "
+                                    f"optical screen is {n_atm}), at most {_abi.IMS_MAX_PSF} fit a launch: drop a psf item or doOpt")
+    try:
+        for name in (optical_system.AOS_FILE, optical_system.MATRIX_FILE, optical_system.NOMINAL_FILE):
+            optical_system.optics_data_path(data_dir, name)
+    except optical_system.OpticsDataError as e:
+        raise GalSimConfigError(str(e)) from None
+    return True
+
+
 def parse_cosmic_rays(out, ev, data_dir):
     """output.cosmic_ray_rate [per s per CCD] / cosmic_ray_catalog (imsim/ccd.py:114-136) -> the CosmicRays to paint, or
     None for a rate of 0"""
@@ -764,6 +808,7 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     opd_kw = parse_opd(out["opd"], ev) if "opd" in out else None     # config errors before any GPU work
     catalogs = parse_catalogs(out, ev, itype)
     crs = parse_cosmic_rays(out, ev, data_dir)
+    parse_atm_psf_options(inp.get("atm_psf"), stamp_cfg, ev, data_dir, res, itype, cfg.get("psf"))
     tel_cfg = inp.get("telescope", {})
     build_telescope(tel_cfg, ev, band)                                  # ... the telescope's among them
 
@@ -801,11 +846,15 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
                                       {"t0": float, "exptime": float, "kcrit": float, "screen_size": float, "screen_scale": float,
                                        "doOpt": bool, "exponent": float, "nproc": int, "save_file": str, "_no2k": bool})
             import torch
-            cfg["_atm_psf"] = atm_psf.AtmosphericPSF(float(a["airmass"]), float(a["rawSeeing"]), a["band"], seed=seed,
-                                                     t0=float(a.get("t0", 0.0)), exptime=float(a.get("exptime", 30.0)),
-                                                     kcrit=float(a.get("kcrit", 0.2)), screen_size=float(a.get("screen_size", 819.2)),
-                                                     screen_scale=float(a.get("screen_scale", 0.1)), exponent=float(a.get("exponent", -0.3)),
-                                                     device=torch.device(device))
+            do_opt = bool(a.get("doOpt", False))
+            try:
+                cfg["_atm_psf"] = atm_psf.AtmosphericPSF(float(a["airmass"]), float(a["rawSeeing"]), a["band"], seed=seed,
+                                                         t0=float(a.get("t0", 0.0)), exptime=float(a.get("exptime", 30.0)),
+                                                         kcrit=float(a.get("kcrit", 0.2)), screen_size=float(a.get("screen_size", 819.2)),
+                                                         screen_scale=float(a.get("screen_scale", 0.1)), exponent=float(a.get("exponent", -0.3)),
+                                                         device=torch.device(device), doOpt=do_opt, data_dir=data_dir)
+            except optical_system.OpticsDataError as e:
+                raise GalSimConfigError(str(e)) from None
         r2, cdf = configs.standard_tables()
         psf, kpsf, fwhm_total, atm, extra_ktables = build_psf(cfg["psf"], ev, {"kolmogorov": 2})
         if atm is not None:

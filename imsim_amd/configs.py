@@ -378,14 +378,15 @@ def field_angles(scene, x, y):
     return thx, thy
 
 
-def scene_c3b(nx=4096, ny=4096, seed=398414, sensor=True, screen_size=819.2, screen_scale=0.1, device=None, **kw):
+def scene_c3b(nx=4096, ny=4096, seed=398414, sensor=True, screen_size=819.2, screen_scale=0.1, device=None, optical=None, **kw):
     """C3b: C3 with the default config's 6-screen AtmosphericPSF (config/imsim-config.yaml:239-256):
-    Convolve[AtmosphericPSF (phase screens + second kick), Gaussian fwhm 0.3]."""
+    Convolve[AtmosphericPSF (phase screens + second kick), Gaussian fwhm 0.3].  optical: keyword arguments of
+    AtmosphericPSF's optical phase screen (doOpt, data_dir, optical_deviations, optical_nominal); None = atm_psf.doOpt false."""
     from . import atm_psf
     sc = scene_c3(nx=nx, ny=ny, seed=seed, sensor=sensor, **kw)
     atm = atm_psf.AtmosphericPSF(VISIT["airmass"], VISIT["raw_seeing"], VISIT["band"], seed=seed,
                                  exptime=VISIT["exptime"], screen_size=screen_size, screen_scale=screen_scale,
-                                 device=device)
+                                 device=device, **(optical or {}))
     r2, cdf = sc.radial_r2, sc.radial_cdf
     sk = atm.second_kick
     sc.radial_r2 = np.concatenate([r2, sk[0][None, :]])

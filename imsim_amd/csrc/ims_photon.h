@@ -244,10 +244,13 @@ IMS_DEV void screen_gradient(const ims_atmosphere_t& A, double pu, double pv, do
 }
 
 // KIND >= 0: the component's kind as a compile-time constant (kernels specialised for a PSF, run_psf<>)
-template <int KIND = -1>
-IMS_DEV void apply_psf(const ims_render_params_t& P, const ims_object_t& o, int comp, int64_t k, Rng& rng, Photon& ph)
+// RIDX: the component's deviates are addressed by `ridx` instead of its place in the list (lists that hold an optical phase
+// screen, which is transparent to the addressing: run_psf<3>, <4>); the kernels without one pass nothing and compile as before
+template <int KIND = -1, bool RIDX = false>
+IMS_DEV void apply_psf(const ims_render_params_t& P, const ims_object_t& o, int comp_in, int64_t k, Rng& rng, Photon& ph, int ridx = 0)
 {
-    const ims_psf_component_t& c = P.psf[comp];
+    const ims_psf_component_t& c = P.psf[comp_in];
+    const int comp = RIDX ? ridx : comp_in;
     const int kind = (KIND >= 0) ? KIND : c.kind;
     rng_block(rng, P.seed, o.obj_id, k, SLOT_PSF + ((uint32_t)comp >> 1));
     const uint32_t wa = (comp & 1) ? rng.w[2] : rng.w[0], wb = (comp & 1) ? rng.w[3] : rng.w[1];
@@ -293,8 +296,12 @@ IMS_DEV void apply_psf(const ims_render_params_t& P, const ims_object_t& o, int 
     ph.y = ph.y + (o.winv[2] * ku + o.winv[3] * kv);
 }
 
+#include "ims_optical.h"
+
 // The PSF components of a launch.  PSF 0: whatever the descriptor lists; 1: a radial-table profile then a Gaussian (imSim's
 // analytic atmosphere: Kolmogorov (+) Gaussian) as straight-line code.  The host checks the descriptor.
+// PSF 3: whatever the descriptor lists, an optical phase screen among it (the workgroup has run optical_setup); 4: imSim's
+// AtmosphericPSF with doOpt -- phase screens, second kick, optical screen, Gaussian -- as straight-line code.
 template <int PSF>
 IMS_DEV void run_psf(const ims_render_params_t& P, const ims_object_t& o, int64_t k, Rng& rng, Photon& ph)
 {
@@ -306,6 +313,20 @@ IMS_DEV void run_psf(const ims_render_params_t& P, const ims_object_t& o, int64_
         apply_psf<IMS_PSF_SCREENS>(P, o, 0, k, rng, ph);
         apply_psf<IMS_PSF_RADIAL>(P, o, 1, k, rng, ph);
         apply_psf<IMS_PSF_GAUSSIAN>(P, o, 2, k, rng, ph);
+    } else if (PSF == 3) {
+        int ridx = 0;
+        bool have_pupil = false;
+        for (int c = 0; c < P.n_psf; ++c) {
+            if (P.psf[c].kind == IMS_PSF_OPTICAL_SCREEN) { apply_psf_optical(P, o, c, k, have_pupil, rng, ph); continue; }
+            apply_psf<-1, true>(P, o, c, k, rng, ph, ridx);
+            have_pupil = have_pupil || P.psf[c].kind == IMS_PSF_SCREENS;
+            ++ridx;
+        }
+    } else if (PSF == 4) {
+        apply_psf<IMS_PSF_SCREENS>(P, o, 0, k, rng, ph);
+        apply_psf<IMS_PSF_RADIAL>(P, o, 1, k, rng, ph);
+        apply_psf_optical(P, o, 2, k, true, rng, ph);
+        apply_psf<IMS_PSF_GAUSSIAN, true>(P, o, 3, k, rng, ph, 2);
     } else {
         for (int c = 0; c < P.n_psf; ++c) apply_psf(P, o, c, k, rng, ph);
     }

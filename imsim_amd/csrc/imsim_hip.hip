@@ -351,6 +351,7 @@ __global__ __launch_bounds__(256, (CHAIN == 1) ? IMS_CHAIN_WAVES : IMS_FUSED_WAV
     // Wavefronts of the workgroup that hold no photon of this segment (a 19-photon object uses one of four) leave at
     // once: they would only sit in the barriers and keep the wave slots other segments could run in.  The hardware
     // barrier counts the waves that are still alive.
+    if constexpr (PSF >= 3) optical_setup(P, o);     // the object's optical phase screen, by all 256 threads (ims_optical.h)
     const int n_thr = (((int)(j1 - j0) + 63) >> 6) << 6;
     if ((int)threadIdx.x >= n_thr) return;
     const bool silicon = (P.sensor != nullptr) && (P.sensor->kind == IMS_SENSOR_SILICON);
@@ -400,6 +401,7 @@ __global__ __launch_bounds__(256, (CHAIN == 1) ? IMS_CHAIN_WAVES : IMS_FUSED_WAV
     if (seg >= P.n_segments) return;
     const int64_t oi = P.seg_object ? (int64_t)P.seg_object[seg] : find_object(P.seg_prefix, P.n_objects, seg);
     const ims_object_t& o = P.objects[oi];
+    if constexpr (PSF >= 3) optical_setup(P, o);     // the object's optical phase screen, by all 256 threads (ims_optical.h)
     const int64_t j = (seg - P.seg_prefix[oi]) * P.seg_size + threadIdx.x;
     if (j >= o.n_phot) return;
     const int64_t k = o.phot_first + j;
@@ -3229,6 +3231,26 @@ __global__ void k_test_math(int which, const double* __restrict__ in, double* __
     }
 }
 
+// the optical phase screen's device functions (ims_optical.h) on n independent points, one thread each: the same functions, in
+// the same order, as optical_setup and apply_psf_optical run them (there a workgroup shares the per-object part through LDS)
+__global__ __launch_bounds__(256) void k_test_optical_screen(const ims_optical_screen_t* __restrict__ screen,
+                                                             const double* __restrict__ thx, const double* __restrict__ thy,
+                                                             const double* __restrict__ u, const double* __restrict__ v, int64_t n,
+                                                             double* __restrict__ coef, double* __restrict__ dwdu,
+                                                             double* __restrict__ dwdv)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    OptScreenPtr S = (OptScreenPtr)screen;
+    const double tx = optical_theta(S, thx[i]), ty = optical_theta(S, thy[i]);
+    double a[IMS_OPT_NZ], gxc[21], gyc[21];
+    for (int j = 0; j < IMS_OPT_NZ; ++j) { a[j] = optical_coeff(S, j, tx, ty); coef[i * IMS_OPT_NZ + j] = a[j]; }
+    for (int t = 0; t < IMS_OPT_NPUPIL; ++t) optical_gradient_coeff(t, optical_pupil_coeff(S, (const double*)a, t), (double*)gxc, (double*)gyc);
+    double gx, gy;
+    optical_gradient((const double*)gxc, (const double*)gyc, S->inv_r, S->grad_scale, u[i], v[i], gx, gy);
+    dwdu[i] = gx; dwdv[i] = gy;
+}
+
 // ---------------- host side of the C-ABI ----------------
 static int check_params(const ims_render_params_t* p)
 {
@@ -3240,6 +3262,18 @@ static int check_params(const ims_render_params_t* p)
     if (p->n_ops < 0 || p->n_ops > IMS_MAX_OPS) return set_err(IMS_ERR_ARG, "n_ops out of range");
     for (int k = 0; k < p->n_psf; ++k)
         if (p->psf[k].kind == IMS_PSF_SCREENS && !p->atm) return set_err(IMS_ERR_ARG, "phase-screen PSF without atmosphere descriptor");
+    int n_optical = 0;
+    for (int k = 0; k < p->n_psf; ++k) {
+        if (p->psf[k].kind != IMS_PSF_OPTICAL_SCREEN) continue;
+        if (!p->atm) return set_err(IMS_ERR_ARG, "optical phase screen without its descriptor (atm must point to an ims_atmosphere_optical_t)");
+        if (p->psf[k].chrom_alpha != 0.0) return set_err(IMS_ERR_ARG, "the optical phase screen is achromatic (chrom_alpha must be 0)");
+        if (++n_optical > 1) return set_err(IMS_ERR_ARG, "more than one optical phase screen");
+        // the phase screens address their deviates by their place among the components that are not the optical screen, the
+        // pre-pass (ims_screen_prepass) by their place in the list: the same only while the optical screen comes after them
+        for (int c = k + 1; c < p->n_psf; ++c)
+            if (p->psf[c].kind == IMS_PSF_SCREENS)
+                return set_err(IMS_ERR_ARG, "the optical phase screen must come after the IMS_PSF_SCREENS component (the order of AtmosphericPSF.getPSF)");
+    }
     for (int k = 0; k < p->n_ops; ++k) {
         const int kind = p->ops[k].kind;
         if ((kind == IMS_OP_RUBIN_OPTICS || kind == IMS_OP_RUBIN_DIFFRACTION || kind == IMS_OP_RUBIN_DIFFRACTION_OPTICS) && !p->optics)
@@ -3338,8 +3372,22 @@ static bool is_default_chain(const ims_render_params_t* p)
 // AtmosphericPSF); 0: anything else.  (Variant 2 is slower than the component loop at four workgroups per CU -- C3b 36.9 -> 38.6 ms
 // in round 2, 35.2 -> 35.9 ms now -- and faster at the three that launches with phase screens run with (photon_lds_pad):
 // 33.7 -> 33.2 ms.  ims_tuning_t.psf_screens_kernel = 0 takes the loop.)
+// 3: a list with an optical phase screen (IMS_PSF_OPTICAL_SCREEN) in it (run_psf<3>); 4: screens, second kick, optical screen,
+// Gaussian -- AtmosphericPSF with doOpt (run_psf<4>), taken under the same switches as variant 2.  Lists without the component
+// never reach a kernel compiled for it, and the other way round (a missing kernel is not replaced by another).
+static bool has_optical_screen(const ims_render_params_t* p)
+{
+    for (int c = 0; c < p->n_psf; ++c)
+        if (p->psf[c].kind == IMS_PSF_OPTICAL_SCREEN) return true;
+    return false;
+}
 static int psf_variant(const ims_render_params_t* p)
 {
+    if (has_optical_screen(p)) {
+        if (g_tune.chain_kernels && g_tune.psf_screens_kernel && p->n_psf == 4 && p->psf[0].kind == IMS_PSF_SCREENS &&
+            p->psf[1].kind == IMS_PSF_RADIAL && p->psf[2].kind == IMS_PSF_OPTICAL_SCREEN && p->psf[3].kind == IMS_PSF_GAUSSIAN) return 4;
+        return 3;
+    }
     if (!g_tune.chain_kernels) return 0;
     if (p->n_psf == 2 && p->psf[0].kind == IMS_PSF_RADIAL && p->psf[1].kind == IMS_PSF_GAUSSIAN) return 1;
     if (g_tune.psf_screens_kernel && p->n_psf == 3 && p->psf[0].kind == IMS_PSF_SCREENS && p->psf[1].kind == IMS_PSF_RADIAL &&
@@ -3417,6 +3465,15 @@ int ims_shoot_accumulate(const ims_render_params_t* params_in, void* stream)
         const dim3 grid(grid_for_segments(params->n_segments));
         const int pv = is_default_chain(params) ? psf_variant(params) : -1;
         const bool lay = pv >= 0 && params->optics_layout == IMS_LAYOUT_RUBIN_LIKE && g_tune.layout_kernels != 0;
+        // lists with an optical phase screen: the straight-line kernel of AtmosphericPSF(doOpt) on the default chain and layout,
+        // else the loops over components, operators and surfaces
+        if (has_optical_screen(params)) {
+            if (params->optics_layout == IMS_LAYOUT_PERTURBED)
+                hipLaunchKernelGGL((k_shoot_accumulate<0, 3, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params);
+            else if (pv == 4 && lay)
+                hipLaunchKernelGGL((k_shoot_accumulate<1, 4, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params);
+            else hipLaunchKernelGGL((k_shoot_accumulate<0, 3>), grid, dim3(256), photon_lds_pad(params), st, *params);
+        } else
         // a perturbed telescope (include/imsim_hip.h): the loops over the operators and the surfaces, every surface in its frame
         if (params->optics_layout == IMS_LAYOUT_PERTURBED)
             hipLaunchKernelGGL((k_shoot_accumulate<0, 0, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params);
@@ -3446,6 +3503,10 @@ int ims_shoot_photons(const ims_render_params_t* params, const int64_t* photon_o
     if (params->n_segments == 0) return IMS_OK;
     hipStream_t st = (hipStream_t)stream;
     {
+        if (has_optical_screen(params))
+            hipLaunchKernelGGL((k_shoot_photons<0, 0, 3>), dim3(grid_for_segments(params->n_segments)), dim3(256), 0, st,
+                               *params, photon_offset, *pool);
+        else
         hipLaunchKernelGGL((k_shoot_photons<0, 0>), dim3(grid_for_segments(params->n_segments)), dim3(256), 0, st,
                            *params, photon_offset, *pool);
     }
@@ -3469,6 +3530,16 @@ int ims_shoot_ops_photons(const ims_render_params_t* params, const int64_t* phot
         const int pv = is_default_chain(params) ? psf_variant(params) : -1;
         const bool lay = pv >= 0 && params->optics_layout == IMS_LAYOUT_RUBIN_LIKE && g_tune.layout_kernels != 0;
         const bool pert = params->optics_layout == IMS_LAYOUT_PERTURBED;
+        if (has_optical_screen(params)) {
+            if (pool->converted && pert)
+                hipLaunchKernelGGL((k_shoot_photons<2, 0, 3, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
+            else if (pert)
+                hipLaunchKernelGGL((k_shoot_photons<1, 0, 3, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
+            else if (pool->converted && pv == 4 && lay)
+                hipLaunchKernelGGL((k_shoot_photons<2, 1, 4, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
+            else if (pool->converted) hipLaunchKernelGGL((k_shoot_photons<2, 0, 3>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
+            else hipLaunchKernelGGL((k_shoot_photons<1, 0, 3>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
+        } else
         if (pool->converted && pert)
             hipLaunchKernelGGL((k_shoot_photons<2, 0, 0, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
         else if (pert)
@@ -5253,6 +5324,8 @@ int ims_struct_size(int which)
     case 25: return (int)sizeof(ims_perturbation_t);
     case 26: return (int)sizeof(ims_cr_span_t);
     case 27: return (int)sizeof(ims_cr_hit_t);
+    case 28: return (int)sizeof(ims_optical_screen_t);
+    case 29: return (int)sizeof(ims_atmosphere_optical_t);
     }
     return -1;
 }
@@ -5311,6 +5384,17 @@ int ims_test_math(int which, const double* in_dev, double* out_dev, int64_t n, u
     if (n <= 0) return IMS_OK;
     hipLaunchKernelGGL(k_test_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        which, in_dev, out_dev, n, seed, obj, slot);
+    HIP_TRY(hipGetLastError());
+    return IMS_OK;
+}
+
+int ims_test_optical_screen(const ims_optical_screen_t* screen_dev, const double* thx, const double* thy, const double* u,
+                            const double* v, int64_t n, double* coef, double* dwdu, double* dwdv, void* stream)
+{
+    if (n <= 0) return IMS_OK;
+    if (!screen_dev || !thx || !thy || !u || !v || !coef || !dwdu || !dwdv) return set_err(IMS_ERR_ARG, "optical screen probe: NULL argument");
+    hipLaunchKernelGGL(k_test_optical_screen, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       screen_dev, thx, thy, u, v, n, coef, dwdu, dwdv);
     HIP_TRY(hipGetLastError());
     return IMS_OK;
 }

@@ -659,6 +659,12 @@ class BoundScene:
             else:
                 _, P.optics = mem.put_struct(opt)
                 P.optics_layout = optics_layout(opt)
+        if any(int(c[0]) == _abi.IMS_PSF_OPTICAL_SCREEN for c in scene.psf):
+            # the optical phase screen (AtmosphericPSF(doOpt=True)): its block travels behind the atmosphere descriptor
+            if not isinstance(mem, DeviceMem):
+                raise ValueError("the optical phase screen is shot by the library's kernels only (the CPU oracle has no such component)")
+            if scene.atm is None or getattr(scene.atm, "opt", None) is None:
+                raise ValueError("an IMS_PSF_OPTICAL_SCREEN component needs scene.atm to be an AtmosphericPSF built with doOpt=True")
         if scene.atm is not None:
             A = scene.atm.atmosphere_struct()
             scr = scene.atm.screens

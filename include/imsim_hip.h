@@ -69,6 +69,10 @@ extern "C" {
                                p0 = arcsec per (nm/m) of wavefront gradient = 1e-9 * 206265; also samples pupil_u/v and time */
 #define IMS_PSF_DOUBLE_GAUSSIAN 4  /* imsim DoubleGaussianPSF (atmPSF.py:448-486): Gaussian of sigma p0 with probability p2,
                                     * else of sigma p1 [arcsec] */
+#define IMS_PSF_OPTICAL_SCREEN 5   /* the optical phase screen of AtmosphericPSF(doOpt=True) (imsim/atmPSF.py:37-76, :323-334): a static,
+                                    * achromatic wavefront of annular Zernikes Z4 .. Z22 whose coefficients vary over the field
+                                    * (ims_optical_screen_t below; `atm` must then point to an ims_atmosphere_optical_t);
+                                    * p0 = arcsec per (nm/m) of wavefront gradient, as for IMS_PSF_SCREENS; chrom_alpha must be 0 */
 #define IMS_MAX_PSF 4
 
 /* ---- photon-op kinds (names follow the registered PhotonOp types) ---- */
@@ -222,6 +226,45 @@ typedef struct ims_atmosphere {
      * kernel of C3b moved 22 GB per launch that way).  Same sample values, same arithmetic, 4 x the memory. */
     const float IMS_G* screen_quads;
 } ims_atmosphere_t;
+
+/* ---- the optical phase screen (IMS_PSF_OPTICAL_SCREEN) ----
+ * imSim's OptWF: the residual aberrations of the telescope as one more phase screen.  For an object at field angle
+ * (atm_tan_x, atm_tan_y) [rad]
+ *   th    = ((atm_tan * 57.29577951308232) * remap)                      degrees, remapped (1.708 / 2.04, atmPSF.py:67)
+ *   a_j   = sum_{p + q <= 4} field[j][IMS_OPT_ROW(4, q) + p] thx^p thy^q        j = 0 .. 18: annular Z4 .. Z22, waves at lam0
+ *   w_t   = sum_j a_j pupil[j][t]                                               t = IMS_OPT_ROW(6, q) + p: x^p y^q, p + q <= 6
+ *   W(u, v) = lam0 sum_t w_t x^p y^q,  (x, y) = (u, v) * inv_r                  [nm]
+ * and a photon entering the pupil at (u, v) [m] is kicked by p0 * grad_scale * (dP/dx, dP/dy), P = sum_t w_t x^p y^q.
+ * (u, v) are the pupil coordinates an IMS_PSF_SCREENS component earlier in the list drew for the photon (GalSim samples the
+ * pupil once per photon for all phase screens); without one the component draws its own from the annulus of the atmosphere
+ * descriptor, words 0 and 1 of RNG slot SLOT_PSF + 2, which no other component owns.  The component is transparent to the RNG
+ * addressing of the others: a component after it draws the deviates it would draw if the screen were not in the list.
+ * It must come AFTER an IMS_PSF_SCREENS component of the same list (the order of getPSF; refused otherwise), and a list holds one.
+ * Order of operations (numerics spec v6, f64, no contraction): a_j and each row of it by Horner with separate * and +, the
+ * innermost variable thx, highest power first, then the rows in thy the same way; w_t = a_0 pupil[0][t], then + a_j pupil[j][t]
+ * for j = 1 .. 18 in order; the gradient coefficients (double)p * w_t and (double)q * w_t; the two gradient polynomials
+ * (degree 5, rows IMS_OPT_ROW(5, q)) by the same nested Horner with fma(acc, x, c) steps; then * grad_scale, * p0. */
+#define IMS_OPT_NZ 19
+#define IMS_OPT_NFIELD 15
+#define IMS_OPT_NPUPIL 28
+#define IMS_OPT_ROW(deg, q) ((q) * ((deg) + 1) - (q) * ((q) - 1) / 2)   /* first entry of the row of y^q: x^0 .. x^(deg - q) */
+typedef struct ims_optical_screen {
+    double field[IMS_OPT_NZ][IMS_OPT_NFIELD];   /* monomial coefficients of the field dependence, in remapped degrees */
+    double pupil[IMS_OPT_NZ][IMS_OPT_NPUPIL];   /* annular Zernikes Z4 .. Z22 (obscuration 0.61) as monomials of (x, y) = (u, v) / R */
+    double r_outer;          /* R [m] (4.18) */
+    double remap;            /* 1.708 / 2.04 */
+    double lam0;             /* nm (500: galsim.OpticalScreen's default) */
+    double inv_r;            /* set by the host: 1 / r_outer */
+    double grad_scale;       /* set by the host: lam0 * inv_r, nm/m per unit of the normalised gradient */
+} ims_optical_screen_t;
+
+/* what `atm` points to when the PSF list holds an IMS_PSF_OPTICAL_SCREEN: the atmosphere descriptor (n_layers may be 0 when
+ * no IMS_PSF_SCREENS component is listed; aper_r_outer / aper_r_inner are still the pupil annulus) followed by the screen.
+ * Sizes: ims_struct_size 28 and 29. */
+typedef struct ims_atmosphere_optical {
+    ims_atmosphere_t atm;
+    ims_optical_screen_t opt;
+} ims_atmosphere_optical_t;
 
 typedef struct ims_op {
     int32_t kind;            /* IMS_OP_* */
@@ -1072,7 +1115,7 @@ int  ims_enable_timing(int which);
  * 0 object, 1 radial_tables, 2 lin_tables, 3 psf_component, 4 op, 5 surface, 6 tansip, 7 optics, 8 bf_slot,
  * 9 sensor, 10 photons, 11 render_params, 12 plan_item, 13 atmosphere, 14 fft_object, 15 fft_params, 16 readout,
  * 17 chain, 18 catalog, 19 object_meta, 20 plan_input, 21 plan_sizes, 22 tuning, 23 opd, 24 optics_perturbed, 25 perturbation,
- * 26 cr_span, 27 cr_hit */
+ * 26 cr_span, 27 cr_hit, 28 optical_screen, 29 atmosphere_optical */
 /* Host helpers: fill the derived (uniform) fields of an op / a medium from its primary parameters, so
  * that the kernels do not recompute launch-wide constants per photon.  Call them once when the op
  * chain / the optics descriptor is built; ops and media without derived fields are left untouched. */
@@ -1087,6 +1130,11 @@ int  ims_fill_derived_sensor(ims_sensor_t* sensor);
 int  ims_struct_size(int which);
 int  ims_test_math(int which, const double* in_dev, double* out_dev, int64_t n, uint64_t seed, int64_t obj,
                    uint32_t slot, void* stream);
+/* the same for the optical phase screen: for n points, field angles thx / thy [rad, as ims_object_t.atm_tan_x / _y] and pupil
+ * positions u / v [m] (device arrays) -> coef[n][IMS_OPT_NZ] (a_4 .. a_22, waves), dwdu[n], dwdv[n] [nm/m], from the device
+ * functions the photon kernels call.  screen_dev: a device ims_optical_screen_t. */
+int  ims_test_optical_screen(const ims_optical_screen_t* screen_dev, const double* thx, const double* thy, const double* u,
+                             const double* v, int64_t n, double* coef, double* dwdu, double* dwdv, void* stream);
 
 #ifdef __cplusplus
 }
