@@ -38,9 +38,41 @@ RAFTS = ["R01", "R02", "R03", "R10", "R11", "R12", "R13", "R14", "R20", "R21", "
 SENSORS = ["S00", "S01", "S02", "S10", "S11", "S12", "S20", "S21", "S22"]
 ITL_RAFTS = {"R01", "R02", "R03", "R10", "R20", "R41", "R42", "R43"}
 
+# Nominal focal-plane layout: rafts on a 127 mm pitch, CCDs on a 42.25 mm pitch inside a raft, 10 micron pixels, R22_S11 at
+# the origin, no rotations of the science rafts.  The per-CCD metrology of lsst.obs.lsst (which the reference asks
+# lsst.afw.cameraGeom for) is not available; this layout stands in for it.
+RAFT_PITCH_MM = 127.0
+CCD_PITCH_MM = 42.25
+PIXEL_MM = 0.01
+PIXELS_PER_MM = 100.0
+
 
 def det_type_of(det_name):
     return "ITL" if det_name[:3] in ITL_RAFTS else "E2V"
+
+
+def science_ccd_center_mm(det_name, camera_class="LsstCamSim"):
+    """Focal-plane position [mm] of the centre of science CCD 'Rxy_Sxy' of LsstCamSim in the nominal layout.  The corner
+    rafts (wavefront and guider sensors), other cameras and anything that is not a detector name are config errors."""
+    from .lsst_image import GalSimConfigError
+    if camera_class != "LsstCamSim":
+        raise GalSimConfigError(f"detector {det_name}: the focal-plane layout of camera {camera_class} is not known (LsstCamSim only)")
+    raft, _, sensor = str(det_name).partition("_")
+    if raft not in RAFTS or sensor not in SENSORS:
+        kind = "a corner-raft sensor" if raft in ("R00", "R04", "R40", "R44") else "not a science CCD of LsstCamSim"
+        raise GalSimConfigError(f"detector {det_name} is {kind}: only the science rafts have a focal-plane position here")
+    rx, ry = int(raft[1]), int(raft[2])
+    sx, sy = int(sensor[1]), int(sensor[2])
+    return ((rx - 2) * RAFT_PITCH_MM + (sx - 1) * CCD_PITCH_MM, (ry - 2) * RAFT_PITCH_MM + (sy - 1) * CCD_PITCH_MM)
+
+
+def fp_to_pix(det_name, nx, ny, camera_class="LsstCamSim"):
+    """The focal-plane [mm] -> pixel affine (m0 .. m5) of optics.make_optics / fill_optics for a science CCD of nx x ny pixels:
+    x_pix = 100 (fpx - cx_mm) + cx_pix with cx_pix = (nx - 1) / 2 + 0.5 the CCD's centre, the same in y.  R22_S11 sits on the
+    optical axis: (100, 0, cx_pix, 0, 100, cy_pix)."""
+    cx_mm, cy_mm = science_ccd_center_mm(det_name, camera_class)
+    cx_pix, cy_pix = (nx - 1) / 2.0 + 0.5, (ny - 1) / 2.0 + 0.5
+    return (PIXELS_PER_MM, 0.0, cx_pix - PIXELS_PER_MM * cx_mm, 0.0, PIXELS_PER_MM, cy_pix - PIXELS_PER_MM * cy_mm)
 
 
 class Amp:

@@ -40,6 +40,7 @@ def RegisterValueType(name, builder): valid_value_types[name] = builder
 def RegisterTemplate(name, path): templates[name] = path
 
 
+from . import camera as cameramod                                # noqa: E402
 from .camera import RAFTS, SENSORS, ITL_RAFTS, det_type_of      # noqa: E402  (one table of the focal-plane layout)
 
 
@@ -734,6 +735,43 @@ def _process_opd(opd_cfg, kw, ev, out, tel, wl_eff, det_nums, res, device):
         res.files.append(fn)
 
 
+# image.wcs type Batoid: the reference builder's parameter surface (imsim/batoid_wcs.py:530-543)
+WCS_REQ = {"boresight": None, "obstime": None, "det_name": str}
+WCS_OPT = {"camera": str, "telescope": str, "temperature": float, "pressure": float, "H2O_pressure": float, "wavelength": float,
+           "order": int}
+WCS_IGNORED = {
+    "obstime": "image.wcs.obstime (the sky rotation comes from the visit's rotSkyPos; no precession or nutation is applied)",
+    "telescope": "image.wcs.telescope (the WCS is traced through the visit's one telescope, input.telescope)",
+    "temperature": "image.wcs.temperature (no atmospheric refraction in the ICRF -> field step)",
+    "pressure": "image.wcs.pressure (no atmospheric refraction in the ICRF -> field step)",
+    "H2O_pressure": "image.wcs.H2O_pressure (no atmospheric refraction in the ICRF -> field step)",
+}
+
+
+def parse_image_wcs(image, res=None):
+    """`image.wcs`: None when absent (the CCD is rendered on the optical axis, as ever); type Batoid -> its dict, keys checked
+    against the reference builder's required and optional sets, the ones this path cannot honour noted in res.ignored; any
+    other type is refused.  The values stay unevaluated: det_name, boresight and wavelength may differ per CCD."""
+    wcs_cfg = image.get("wcs")
+    if wcs_cfg in (None, ""):
+        return None
+    if not isinstance(wcs_cfg, dict):
+        raise GalSimConfigError("image.wcs must be a dict")
+    t = wcs_cfg.get("type", "PixelScale")
+    if t != "Batoid":
+        raise GalSimConfigError(f"image.wcs type {t} is not supported on this path: only type Batoid (the WCS traced through "
+                                "the telescope) is built")
+    try:
+        lsst_image.get_all_params({k: v for k, v in wcs_cfg.items() if k != "type"}, WCS_REQ, WCS_OPT)
+    except GalSimConfigError as e:
+        raise GalSimConfigError(f"image.wcs: {e}") from None
+    if res is not None:
+        for k, note in WCS_IGNORED.items():
+            if k in wcs_cfg and note not in res.ignored:
+                res.ignored.append(note)
+    return wcs_cfg
+
+
 def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=None, logger=None, rank=0, world=1):
     """galsim.config.Process restricted to this path: reads inputs, then for every requested CCD
     builds the scene and runs the image builder on the GPU.  Returns a ProcessResult.
@@ -811,6 +849,7 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     parse_atm_psf_options(inp.get("atm_psf"), stamp_cfg, ev, data_dir, res, itype, cfg.get("psf"))
     tel_cfg = inp.get("telescope", {})
     build_telescope(tel_cfg, ev, band)                                  # ... the telescope's among them
+    wcs_cfg = parse_image_wcs(image, res)
 
     def prepare(det):
         """Host half of one CCD: scene, catalog, object classification -- everything up to the first GPU call of the CCD
@@ -829,16 +868,38 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
         # (perturbations and focusZ included: the photons, the WCS pair and the opd / sag outputs all see the same telescope)
         tel = build_telescope(tel_cfg, ev, band, res)
         rot_tel = math.radians(meta.get("rotTelPos") or 0.0)
-        fp = (100.0, 0.0, (nx - 1) / 2.0 + 0.5, 0.0, 100.0, (ny - 1) / 2.0 + 0.5)
-        optics = opticsmod.make_optics(tel, fp, rot_tel)
-        ra0, dec0 = math.radians(meta.get("fieldRA") or 0.0), math.radians(meta.get("fieldDec") or 0.0)
-        optics.img_wcs, optics.icrf_to_field, _ = opticsmod.build_wcs_pair(
-            tel, fp, ra0, dec0, rot_sky=math.radians(meta.get("rotSkyPos") or 0.0), rot_tel_pos=rot_tel, nx=nx, ny=ny)
         # bandpass: the real tables are external data (imsim/bandpass.py); synthetic stand-in
         wl, thr = tables.synthetic_r_band()
         res.ignored.append("image.bandpass (rubin_sim throughputs not present: synthetic r-band table)")
         wl_eff = tables.effective_wavelength(wl, thr)
         ev.vars["bandpass"] = tables.Bandpass(wl, thr)
+        ra0, dec0 = math.radians(meta.get("fieldRA") or 0.0), math.radians(meta.get("fieldDec") or 0.0)
+        rot_sky = math.radians(meta.get("rotSkyPos") or 0.0)
+        if wcs_cfg is None:
+            # no image.wcs: the CCD sits on the optical axis whatever its name, its WCS traced on the host
+            fp = (100.0, 0.0, (nx - 1) / 2.0 + 0.5, 0.0, 100.0, (ny - 1) / 2.0 + 0.5)
+            optics = opticsmod.make_optics(tel, fp, rot_tel)
+            optics.img_wcs, optics.icrf_to_field, _ = opticsmod.build_wcs_pair(
+                tel, fp, ra0, dec0, rot_sky=rot_sky, rot_tel_pos=rot_tel, nx=nx, ny=ny)
+        else:
+            # image.wcs type Batoid: the CCD at its focal-plane position, its WCS pair traced on the GPU
+            w = {k: ev.value(v) for k, v in wcs_cfg.items()}
+            wcs_det = str(w["det_name"])
+            fp = cameramod.fp_to_pix(wcs_det, nx, ny, str(w.get("camera", "LsstCamSim")))
+            bs = w["boresight"]
+            if not isinstance(bs, (tuple, list)) or len(bs) != 2:
+                raise GalSimConfigError(f"image.wcs.boresight: expected a sky position (type RADec), got {bs!r}")
+            ra0, dec0 = float(bs[0]), float(bs[1])
+            if not 1 <= int(w.get("order", 3)) <= 4:
+                raise GalSimConfigError(f"image.wcs.order: {w['order']} is outside 1 .. 4 (the TAN-SIP the kernels evaluate)")
+            optics = opticsmod.make_optics(tel, fp, rot_tel)
+            try:
+                optics.img_wcs, optics.icrf_to_field, _ = opticsmod.build_wcs_pair(
+                    tel, fp, ra0, dec0, rot_sky=rot_sky, rot_tel_pos=rot_tel, nx=nx, ny=ny,
+                    wave_nm=float(w["wavelength"]) if "wavelength" in w else 620.0, order=int(w.get("order", 3)), device=device,
+                    what=f"CCD {wcs_det}")
+            except ValueError as e:
+                raise GalSimConfigError(f"image.wcs: {e}") from None
         # inputs that depend on the exposure
         if "atm_psf" in inp:
             a = {k: ev.value(v) for k, v in inp["atm_psf"].items()}

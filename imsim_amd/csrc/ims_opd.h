@@ -321,4 +321,60 @@ __global__ __launch_bounds__(256) void k_opd_zk_final(const ims_opd_t P, OpdLayo
     }
 }
 
+// ---------------- batched field-point trace (ims_trace_field_points: the points a CCD's WCS is fitted through) ----------------
+// One workgroup per field angle.  Thread t traces pupil rays t, t + 256, ... of the caller's table from the stop plane, every
+// intersection resolved to f64 (trace_step<-1, -1, true>, or trace_step_pert with the detector hit kept in the detector's
+// frame), and adds the detector hits of the rays that are neither vignetted nor lost in ray order; the workgroup's sums go
+// through opd_block_sum's fixed tree in LDS, and thread 0 turns the mean hit into a pixel position the way rubin_op does
+// (camera rotator, focal plane [mm] with x and y swapped, the fp_to_pix affine).  No atomics: a field's result depends
+// neither on the other fields of the call nor on the run.
+template <bool PERT>
+__global__ __launch_bounds__(256) void k_trace_field_points(const ims_optics_t* __restrict__ optics, const double* __restrict__ thx,
+                                                            const double* __restrict__ thy, double wave_nm,
+                                                            const double* __restrict__ pupil_xy, int n_rays,
+                                                            double* __restrict__ xy_out, int32_t* __restrict__ ngood_out)
+{
+    __shared__ double lds[OPD_WG];
+    const ims_optics_t& o = *optics;
+    const int64_t f = blockIdx.x;
+    const double tx = thx[f], ty = thy[f];
+    double n_in;
+    if (o.in_medium_kind == IMS_MEDIUM_CONST) n_in = o.in_medium_c[0];
+    else n_in = medium_n(o.in_medium_kind, o.in_medium_c, wave_nm);
+    // the plane wave of field (tx, ty): direction (tx, ty, -1) / sqrt(1 + tx^2 + ty^2), speed 1 / n_in (optics.pupil_rays)
+    const double g = 1.0 / sqrt(1.0 + tx * tx + ty * ty);
+    const double v0[3] = { tx * g / n_in, ty * g / n_in, -g / n_in };
+    double sx = 0.0, sy = 0.0, cnt = 0.0;
+    for (int r = threadIdx.x; r < n_rays; r += OPD_WG) {
+        TraceState st;
+        st.vignetted = 0;
+        st.n_cur = n_in;
+        st.glass_id = -1; st.glass_n = 0.0; st.glass_in = 0.0;
+        double pos[3] = { pupil_xy[2 * r], pupil_xy[2 * r + 1], o.stop_z };
+        double vel[3] = { v0[0], v0[1], v0[2] };
+        bool ok = true;
+        for (int k = 0; k < o.n_surfaces && ok; ++k) {
+            if (PERT) ok = trace_step_pert(o.surf[k], perturbation_of(o).surf[k], st, pos, vel, wave_nm, k == o.n_surfaces - 1);
+            else ok = trace_step<-1, -1, true>(o.surf[k], st, pos, vel, wave_nm);
+        }
+        if (ok && !st.vignetted) { sx += pos[0]; sy += pos[1]; cnt += 1.0; }
+    }
+    sx = opd_block_sum(sx, lds);
+    sy = opd_block_sum(sy, lds);
+    cnt = opd_block_sum(cnt, lds);
+    if (threadIdx.x != 0) return;
+    ngood_out[f] = (int32_t)cnt;
+    if (!(cnt > 0.0)) {
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        xy_out[2 * f] = nan; xy_out[2 * f + 1] = nan;
+        return;
+    }
+    const double mx = sx / cnt, my = sy / cnt;
+    const double c = o.cam_rot[0], s = o.cam_rot[1];
+    const double rx = c * mx + s * my, ry = -s * mx + c * my;
+    const double fpx = ry * 1.0e3, fpy = rx * 1.0e3;
+    xy_out[2 * f] = o.fp_to_pix[0] * fpx + o.fp_to_pix[1] * fpy + o.fp_to_pix[2];
+    xy_out[2 * f + 1] = o.fp_to_pix[3] * fpx + o.fp_to_pix[4] * fpy + o.fp_to_pix[5];
+}
+
 }  // namespace ims

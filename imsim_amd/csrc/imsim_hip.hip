@@ -5378,6 +5378,39 @@ int ims_opd_perturbed(const ims_opd_t* P, const ims_optics_perturbed_t* optics_d
     return opd_run(P, optics_dev ? &optics_dev->optics : nullptr, true, stream);
 }
 
+static int trace_field_points_run(const ims_optics_t* optics_dev, bool pert, const double* thx, const double* thy, int64_t n,
+                                  double wave_nm, const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out,
+                                  void* stream)
+{
+    if (n < 0) return set_err(IMS_ERR_ARG, "trace_field_points: negative n");
+    if (n == 0) return IMS_OK;
+    if (!optics_dev || !thx || !thy || !pupil_xy || !xy_out || !ngood_out) return set_err(IMS_ERR_ARG, "trace_field_points: NULL argument");
+    if (n > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "trace_field_points: too many field points for one call");
+    if (n_rays < 1 || n_rays > IMS_TRACE_MAX_RAYS) return set_err(IMS_ERR_ARG, "trace_field_points: n_rays out of range");
+    if (!(wave_nm > 0.0)) return set_err(IMS_ERR_ARG, "trace_field_points: the wavelength must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    if (pert) hipLaunchKernelGGL((k_trace_field_points<true>), dim3((unsigned)n), dim3(OPD_WG), 0, s, optics_dev, thx, thy, wave_nm,
+                                 pupil_xy, (int)n_rays, xy_out, ngood_out);
+    else hipLaunchKernelGGL((k_trace_field_points<false>), dim3((unsigned)n), dim3(OPD_WG), 0, s, optics_dev, thx, thy, wave_nm,
+                            pupil_xy, (int)n_rays, xy_out, ngood_out);
+    HIP_TRY(hipGetLastError());
+    return IMS_OK;
+}
+
+int ims_trace_field_points(const ims_optics_t* optics_dev, const double* thx, const double* thy, int64_t n, double wave_nm,
+                           const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out, void* stream)
+{
+    return trace_field_points_run(optics_dev, false, thx, thy, n, wave_nm, pupil_xy, n_rays, xy_out, ngood_out, stream);
+}
+
+int ims_trace_field_points_perturbed(const ims_optics_perturbed_t* optics_dev, const double* thx, const double* thy, int64_t n,
+                                     double wave_nm, const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out,
+                                     void* stream)
+{
+    return trace_field_points_run(optics_dev ? &optics_dev->optics : nullptr, true, thx, thy, n, wave_nm, pupil_xy, n_rays, xy_out,
+                                  ngood_out, stream);
+}
+
 int ims_test_math(int which, const double* in_dev, double* out_dev, int64_t n, uint64_t seed, int64_t obj,
                   uint32_t slot, void* stream)
 {

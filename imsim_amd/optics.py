@@ -899,21 +899,132 @@ def field_to_pixel(tel, thx, thy, fp_to_pix, rot_tel_pos=0.0, wave_nm=620.0):
             fp_to_pix[3] * fpx + fp_to_pix[4] * fpy + fp_to_pix[5])
 
 
+class FieldTracer:
+    """The batched field-point trace on the GPU (ims_trace_field_points): the descriptor and the pupil rays of
+    `pupil_rays` uploaded once, then one launch per call.  There is no host fallback."""
+
+    def __init__(self, desc_or_tel, fp_to_pix=None, rot_tel_pos=0.0, wave_nm=620.0, device="cuda:0", pupil=None):
+        import ctypes as C
+        import torch
+        self.lib = _abi.load()
+        if not torch.cuda.is_available():
+            raise _abi.ImsimHipError("the GPU field-point trace needs a GPU (there is no CPU fallback)")
+        if isinstance(desc_or_tel, Telescope):
+            if fp_to_pix is None:
+                raise ValueError("FieldTracer: a Telescope needs fp_to_pix")
+            if pupil is None:
+                pos, _ = pupil_rays(desc_or_tel, 0.0, 0.0, wave_nm=wave_nm)
+                pupil = pos[:, :2]
+            src = make_optics(desc_or_tel, fp_to_pix, rot_tel_pos)
+        else:
+            if pupil is None:
+                raise ValueError("FieldTracer: a filled descriptor does not hold the pupil's radii; give the pupil rays")
+            src = desc_or_tel
+        # a private copy with the derived fields filled, as the engine does before it uploads a descriptor
+        opt = type(src).from_buffer_copy(bytes(src))
+        _abi.check(self.lib.ims_fill_derived_medium(int(opt.in_medium_kind), opt.in_medium_c), "ims_fill_derived_medium")
+        for k in range(opt.n_surfaces):
+            _abi.check(self.lib.ims_fill_derived_medium(int(opt.surf[k].medium_kind), opt.surf[k].medium_c), "ims_fill_derived_medium")
+        _abi.check(self.lib.ims_fill_derived_optics(C.byref(opt)), "ims_fill_derived_optics")
+        self.torch = torch
+        self.dev = torch.device(device)
+        self.perturbed = isinstance(opt, _abi.OpticsPerturbed)
+        self.wave_nm = float(wave_nm)
+        self.opt_dev = torch.from_numpy(np.frombuffer(bytes(opt), dtype=np.uint8).copy()).to(self.dev)
+        pupil = np.ascontiguousarray(np.asarray(pupil, dtype=np.float64).reshape(-1, 2))
+        self.n_rays = len(pupil)
+        self.pupil_dev = torch.from_numpy(pupil).to(self.dev)
+
+    def __call__(self, thx, thy):
+        """(xy [n, 2] pixel positions, ngood [n] rays averaged) of the field angles thx, thy [rad]"""
+        torch = self.torch
+        thx = np.ascontiguousarray(np.atleast_1d(np.asarray(thx, dtype=np.float64)))
+        thy = np.ascontiguousarray(np.atleast_1d(np.asarray(thy, dtype=np.float64)))
+        if thx.shape != thy.shape or thx.ndim != 1:
+            raise ValueError("field_to_pixel_hip: thx and thy must be 1-d arrays of one length")
+        n = len(thx)
+        th = torch.from_numpy(np.stack([thx, thy])).to(self.dev)
+        xy = torch.empty((n, 2), dtype=torch.float64, device=self.dev)
+        ngood = torch.empty(n, dtype=torch.int32, device=self.dev)
+        with torch.cuda.device(self.dev):
+            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            fn = self.lib.ims_trace_field_points_perturbed if self.perturbed else self.lib.ims_trace_field_points
+            _abi.check(fn(self.opt_dev.data_ptr(), th[0].data_ptr(), th[1].data_ptr(), n, self.wave_nm, self.pupil_dev.data_ptr(),
+                          self.n_rays, xy.data_ptr(), ngood.data_ptr(), stream), "ims_trace_field_points")
+        return xy.cpu().numpy(), ngood.cpu().numpy()
+
+
+def field_to_pixel_hip(desc_or_tel, thx, thy, fp_to_pix=None, rot_tel_pos=0.0, wave_nm=620.0, device="cuda:0", pupil=None):
+    """field_to_pixel for arrays of field angles in one GPU launch: (xy [n, 2], ngood [n]).  desc_or_tel: a Telescope (with
+    fp_to_pix and rot_tel_pos, the rays of pupil_rays) or a filled _abi.Optics / OpticsPerturbed (with `pupil`, [n_rays, 2])."""
+    return FieldTracer(desc_or_tel, fp_to_pix, rot_tel_pos, wave_nm, device, pupil)(thx, thy)
+
+
+# 0.2 arcsec per 10 micron pixel: the focal length [m] the paraxial start of build_wcs_pair divides by
+PLATE_FOCAL_M = 1.0e-5 / (0.2 * math.pi / 648000.0)
+
+
+def image_sign(tel):
+    """+1 when the telescope's image is upright (a field angle +thx lands at +x on the detector), -1 when inverted: read off one
+    chief ray from the stop centre, once per Telescope object (kept on it; a copy made by a perturbation finds its own)."""
+    sign = tel.__dict__.get("_image_sign")
+    if sign is None:
+        h = 1e-4
+        g = 1.0 / math.sqrt(1.0 + h * h)
+        n = medium_n(tel.in_medium, np.array([620.0]))[0]
+        p, _, _, _ = trace_numpy(tel, [[0.0, 0.0, tel.stop_z]], [[h * g / n, 0.0, -g / n]], 620.0)
+        sign = tel.__dict__["_image_sign"] = 1.0 if p[0, 0] > 0.0 else -1.0
+    return sign
+
+
+def paraxial_field(tel, fp_to_pix, rot_tel_pos, nx, ny):
+    """Field angle [rad] of the CCD's centre in the paraxial picture: its focal-plane centre (the point fp_to_pix sends to pixel
+    ((nx - 1) / 2 + 0.5, (ny - 1) / 2 + 0.5)) through the rotator and the plate scale.  Exactly (0, 0) for a CCD on the axis.
+    Whether the image is upright or inverted is the telescope's (image_sign)."""
+    m0, m1, m2, m3, m4, m5 = (float(v) for v in fp_to_pix)
+    dx, dy = (nx - 1) / 2.0 + 0.5 - m2, (ny - 1) / 2.0 + 0.5 - m5
+    det = m0 * m4 - m1 * m3
+    fpx, fpy = (m4 * dx - m1 * dy) / det, (m0 * dy - m3 * dx) / det          # [mm]
+    if fpx == 0.0 and fpy == 0.0:
+        return np.zeros(2)
+    rx, ry = fpy * 1e-3, fpx * 1e-3
+    c, s = math.cos(rot_tel_pos), math.sin(rot_tel_pos)
+    x, y = c * rx - s * ry, s * rx + c * ry
+    return np.array([x, y]) / (image_sign(tel) * PLATE_FOCAL_M)
+
+
 def build_wcs_pair(tel, fp_to_pix, boresight_ra, boresight_dec, rot_sky=0.0, rot_tel_pos=0.0,
-                   nx=4096, ny=4004, wave_nm=620.0, order=3):
+                   nx=4096, ny=4004, wave_nm=620.0, order=3, device=None, what="the CCD"):
     """Build (img_wcs, icrf_to_field) consistent with the telescope by ray tracing, as
     imsim/batoid_wcs.py does: icrf_to_field is the TAN projection about the boresight rotated by
-    `rot_sky`; img_wcs is an order-3 TAN-SIP fitted through traced field points over the detector."""
+    `rot_sky`; img_wcs is an order-3 TAN-SIP fitted through traced field points over the detector.
+
+    The search for the detector centre's field angle starts from the paraxial guess (paraxial_field; (0, 0) on the axis).
+    device=None traces on the host (field_to_pixel); with a device the three points of a Newton step are one launch of
+    ims_trace_field_points and the 127 fit points another; the fit stays on the host.  A field point that no ray reaches
+    unvignetted is an error naming `what`."""
     basis = wcsmod.tangent_basis(boresight_ra, boresight_dec, rot_sky)
     icrf_to_field = wcsmod.make_tansip((0.0, 0.0), np.eye(2), basis)
+    if device is None:
+        def trace(points):
+            return np.array([field_to_pixel(tel, a, b, fp_to_pix, rot_tel_pos, wave_nm) for a, b in points])
+    else:
+        tracer = FieldTracer(tel, fp_to_pix, rot_tel_pos, wave_nm, device)
+
+        def trace(points):
+            points = np.asarray(points, dtype=np.float64)
+            xy, ngood = tracer(points[:, 0], points[:, 1])
+            if np.any(ngood == 0):
+                k = int(np.flatnonzero(ngood == 0)[0])
+                raise ValueError(f"WCS of {what}: no ray of field angle ({points[k, 0]:.6g}, {points[k, 1]:.6g}) rad reaches the "
+                                 f"detector unvignetted ({int((ngood == 0).sum())} of {len(points)} points)")
+            return xy
     # field angle of the detector centre by Newton iteration on the traced mapping
     target = np.array([(nx + 1) / 2.0, (ny + 1) / 2.0])
-    th = np.zeros(2)
+    th = paraxial_field(tel, fp_to_pix, rot_tel_pos, nx, ny)
     h = 1e-4
     for _ in range(8):
-        p0 = np.array(field_to_pixel(tel, th[0], th[1], fp_to_pix, rot_tel_pos, wave_nm))
-        px = np.array(field_to_pixel(tel, th[0] + h, th[1], fp_to_pix, rot_tel_pos, wave_nm))
-        py = np.array(field_to_pixel(tel, th[0], th[1] + h, fp_to_pix, rot_tel_pos, wave_nm))
+        p0, px, py = trace([(th[0], th[1]), (th[0] + h, th[1]), (th[0], th[1] + h)])
         J = np.stack([(px - p0) / h, (py - p0) / h], axis=1)
         th = th - np.linalg.solve(J, p0 - target)
     # hexapolar grid of field angles of radius 0.16 deg about the detector centre (batoid_wcs.py:408-427)
@@ -925,7 +1036,7 @@ def build_wcs_pair(tel, fp_to_pix, boresight_ra, boresight_dec, rot_sky=0.0, rot
             a = 2 * math.pi * j / m
             pts.append((th[0] + r * math.cos(a), th[1] + r * math.sin(a)))
     pts = np.array(pts)
-    pix = np.array([field_to_pixel(tel, a, b, fp_to_pix, rot_tel_pos, wave_nm) for a, b in pts])
+    pix = trace(pts)
     vec = wcsmod.tansip_pix_to_vec(icrf_to_field, pts[:, 0], pts[:, 1])
     img_wcs = wcsmod.fit_tansip(pix[:, 0], pix[:, 1], vec, crpix=target, order=order)
     return img_wcs, icrf_to_field, th

@@ -13,10 +13,9 @@ import os
 import numpy as np
 from scipy import interpolate
 
+from .camera import CCD_PITCH_MM, PIXEL_MM, RAFT_PITCH_MM          # the one table of the nominal layout
+
 DATA_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
-RAFT_PITCH_MM = 127.0
-CCD_PITCH_MM = 42.25
-PIXEL_MM = 0.01
 
 
 def detector_center_mm(det_name):

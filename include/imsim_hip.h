@@ -1072,6 +1072,26 @@ int  ims_opd(const ims_opd_t* opd, const ims_optics_t* optics_dev, void* stream)
 /* the same for a perturbed telescope: optics_dev is a device ims_optics_perturbed_t (derived fields filled) */
 int  ims_opd_perturbed(const ims_opd_t* opd, const ims_optics_perturbed_t* optics_dev, void* stream);
 
+/* ---- batched field-point trace: the points a CCD's WCS is fitted through (imsim/batoid_wcs.py:352-373) ----
+ * For each of n field angles (thx[i], thy[i]) [rad; device arrays] the n_rays pupil rays pupil_xy[r] = (x, y) [m; device
+ * [n_rays][2], starting on the plane z = stop_z] of the plane wave (thx, thy, -1) / sqrt(1 + thx^2 + thy^2) are traced to the
+ * detector at wave_nm, every intersection resolved to f64 as in ims_opd.  The detector hits of the rays that are neither
+ * vignetted nor lost are averaged, and the mean goes through the camera rotator (cam_rot) and fp_to_pix exactly as a photon's
+ * hit does: xy_out[i] = (x_pix, y_pix) [device [n][2]], ngood_out[i] = the number of rays averaged [device [n]]; a field with
+ * no good ray gets NaN and 0.  The pupil rays are the caller's table because ims_optics_t does not hold the pupil's radii.
+ * One workgroup per field and fixed-order sums without atomics: a field's result is the same bits in every call, whatever
+ * other fields share it.  Added in ABI version 22 without changing any existing struct or function, so the version number
+ * stays. */
+#define IMS_TRACE_MAX_RAYS (1 << 20)
+/* optics_dev: device ims_optics_t with its derived fields filled (ims_fill_derived_optics) */
+int  ims_trace_field_points(const ims_optics_t* optics_dev, const double* thx, const double* thy, int64_t n, double wave_nm,
+                            const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out, void* stream);
+/* the same for a perturbed telescope (a device ims_optics_perturbed_t whose frames hold the camera rotator: cam_rot is the
+ * identity and the hit is taken in the detector's frame, as the photon trace does) */
+int  ims_trace_field_points_perturbed(const ims_optics_perturbed_t* optics_dev, const double* thx, const double* thy, int64_t n,
+                                      double wave_nm, const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out,
+                                      void* stream);
+
 /* ---- cosmic rays on the e-image (imsim/cosmic_rays.py:paint_cr) ----
  * A footprint of the catalog is a run of spans; a hit paints one footprint (or a run of its spans) at (x0, y0).  Every span
  * pixel lands on image[y0 + row][x0 + col + k] += values[value_offset + k] (k = 0 .. n-1); pixels off the image are dropped.
