@@ -334,7 +334,7 @@ CR_SPAN_STRUCT_INDEX, CR_HIT_STRUCT_INDEX = 26, 27
 OPTICAL_SCREEN_STRUCT_INDEX, ATMOSPHERE_OPTICAL_STRUCT_INDEX = 28, 29
 
 # every symbol include/imsim_hip.h declares
-EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_info", "ims_known_optics_layout",
+EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_info", "ims_known_optics_layout", "ims_photon_kernel_variant",
            "ims_tuning_defaults", "ims_get_tuning", "ims_set_tuning", "ims_shoot_accumulate",
            "ims_shoot_photons", "ims_shoot_ops_photons", "ims_accumulate_segments", "ims_accumulate_small", "ims_accumulate_round", "ims_run_plan",
            "ims_fft_kspace_fill", "ims_fft_finish", "ims_fft_spikes", "ims_fft_spike_table", "ims_apply_ops", "ims_accumulate", "ims_sensor_init_boundaries",
@@ -415,6 +415,7 @@ def load():
     lib.ims_last_kernel_ms.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int)]
     lib.ims_enable_timing.argtypes = [C.c_int]
     lib.ims_known_optics_layout.argtypes = [c_u64]
+    lib.ims_photon_kernel_variant.argtypes = [C.POINTER(RenderParams), c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_u64)]
     lib.ims_build_object_table.argtypes = [C.POINTER(Catalog), c_vp, c_vp, c_vp, c_vp]
     lib.ims_patch_stamp_sizes.argtypes = [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]
     lib.ims_gather_rows.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]

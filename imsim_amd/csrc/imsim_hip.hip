@@ -3288,6 +3288,104 @@ static unsigned grid_for_segments(int64_t n_segments)
     return (unsigned)(per * N_XCD);
 }
 
+// ---- which photon kernel a launch gets: one selector, one table of instantiations ----
+static bool has_optical_screen(const ims_render_params_t* p)
+{
+    for (int c = 0; c < p->n_psf; ++c)
+        if (p->psf[c].kind == IMS_PSF_OPTICAL_SCREEN) return true;
+    return false;
+}
+static bool psf_kinds_are(const ims_render_params_t* p, std::initializer_list<int32_t> kinds)
+{
+    int c = 0;
+    for (const int32_t k : kinds)
+        if (c >= p->n_psf || p->psf[c++].kind != k) return false;
+    return c == p->n_psf;
+}
+
+// The template arguments of k_shoot_accumulate<CHAIN, PSF, LAYOUT> / k_shoot_photons<MODE, CHAIN, PSF, LAYOUT> for a descriptor.
+// mode: 0 ims_shoot_photons, 1 ims_shoot_ops_photons on a pool that keeps directions and wavelengths, 2 the same on a converted
+// pool and the fused kernel.  Reads n_ops, ops[].kind, n_psf, psf[].kind, atm, optics_layout and the tuning block, nothing else.
+// CHAIN 1: the descriptor lists exactly imSim's default photon-op chain (run_ops<1>); only mode 2 has kernels for it.
+// PSF 1: radial table then Gaussian (run_psf<1>); 2: phase screens, second-kick table, Gaussian (run_psf<2>: imSim's default
+// AtmosphericPSF); 0: anything else.  (Variant 2 is slower than the component loop at four workgroups per CU -- C3b 36.9 -> 38.6 ms
+// in round 2, 35.2 -> 35.9 ms now -- and faster at the three that launches with phase screens run with (photon_lds_pad):
+// 33.7 -> 33.2 ms.  ims_tuning_t.psf_screens_kernel = 0 takes the loop.)
+// 3: a list with an optical phase screen (IMS_PSF_OPTICAL_SCREEN) in it (run_psf<3>); 4: screens, second kick, optical screen,
+// Gaussian -- AtmosphericPSF with doOpt (run_psf<4>), taken under the same switches as variant 2.  Lists without the component
+// never reach a kernel compiled for it, and the other way round (a missing kernel is not replaced by another).
+// The straight-line PSF forms 2 and 4 exist only with the unrolled ray trace of a known layout (ims_known_optics_layout): without
+// it variant 2 runs the component loop on the default chain, variant 4 the loops over components, operators and surfaces.
+// A perturbed telescope (include/imsim_hip.h) always takes the loops, every surface traced in its frame.
+struct PhotonVariant { int chain; int psf; unsigned long long layout; };
+static PhotonVariant select_photon_variant(const ims_render_params_t* p, int mode)
+{
+    static const int32_t chain[IMS_DEFAULT_CHAIN_LEN] = { IMS_OP_TIME_SAMPLER, IMS_OP_PUPIL_ANNULUS_SAMPLER, IMS_OP_PHOTON_DCR,
+                                                          IMS_OP_RUBIN_DIFFRACTION_OPTICS, IMS_OP_FOCUS_DEPTH, IMS_OP_REFRACTION };
+    const bool optical = has_optical_screen(p), pert = p->optics_layout == IMS_LAYOUT_PERTURBED;
+    if (mode == 0) return { 0, optical ? 3 : 0, 0ull };
+    if (mode == 1 || pert) return { 0, optical ? 3 : 0, pert ? IMS_LAYOUT_PERTURBED : 0ull };
+    bool dc = p->n_ops == IMS_DEFAULT_CHAIN_LEN && g_tune.chain_kernels;
+    for (int k = 0; dc && k < IMS_DEFAULT_CHAIN_LEN; ++k) dc = p->ops[k].kind == chain[k];
+    const bool lay = dc && p->optics_layout == IMS_LAYOUT_RUBIN_LIKE && g_tune.layout_kernels != 0;
+    const bool screens = g_tune.psf_screens_kernel != 0;
+    if (optical) {
+        if (lay && screens && psf_kinds_are(p, { IMS_PSF_SCREENS, IMS_PSF_RADIAL, IMS_PSF_OPTICAL_SCREEN, IMS_PSF_GAUSSIAN }))
+            return { 1, 4, IMS_LAYOUT_RUBIN_LIKE };
+        return { 0, 3, 0ull };
+    }
+    if (!dc) return { 0, 0, 0ull };
+    if (psf_kinds_are(p, { IMS_PSF_RADIAL, IMS_PSF_GAUSSIAN })) return { 1, 1, lay ? IMS_LAYOUT_RUBIN_LIKE : 0ull };
+    if (lay && screens && p->atm != nullptr && psf_kinds_are(p, { IMS_PSF_SCREENS, IMS_PSF_RADIAL, IMS_PSF_GAUSSIAN }))
+        return { 1, 2, IMS_LAYOUT_RUBIN_LIKE };
+    return { 1, 0, lay ? IMS_LAYOUT_RUBIN_LIKE : 0ull };
+}
+
+// Every (CHAIN, PSF, LAYOUT) the library holds photon kernels for.  ims_shoot_photons (MODE 0) has the two loop forms without a
+// layout, a pool that is not converted (MODE 1) those and their perturbed forms, the fused kernel and MODE 2 all ten.
+#define IMS_PHOTON_VARIANTS_MODE0(X) X(0, 0, 0ull) X(0, 3, 0ull)
+#define IMS_PHOTON_VARIANTS_MODE1(X) IMS_PHOTON_VARIANTS_MODE0(X) X(0, 0, IMS_LAYOUT_PERTURBED) X(0, 3, IMS_LAYOUT_PERTURBED)
+#define IMS_PHOTON_VARIANTS_MODE2(X) IMS_PHOTON_VARIANTS_MODE1(X) X(1, 0, 0ull) X(1, 1, 0ull) X(1, 0, IMS_LAYOUT_RUBIN_LIKE) \
+    X(1, 1, IMS_LAYOUT_RUBIN_LIKE) X(1, 2, IMS_LAYOUT_RUBIN_LIKE) X(1, 4, IMS_LAYOUT_RUBIN_LIKE)
+
+template <int CHAIN, int PSF, unsigned long long LAYOUT>
+struct PhotonKernel { static constexpr int chain = CHAIN, psf = PSF; static constexpr unsigned long long layout = LAYOUT; };
+
+// launch(PhotonKernel<CHAIN, PSF, LAYOUT>{}) for the row of the mode's list that is v: a triple the list does not hold is an
+// error, never another kernel
+template <int MODE, class Launch>
+static int launch_photon_variant(const PhotonVariant& v, Launch&& launch)
+{
+#define IMS_TRY_VARIANT(C, F, L) if (v.chain == C && v.psf == F && v.layout == L) { launch(PhotonKernel<C, F, L>{}); return IMS_OK; }
+    if constexpr (MODE == 0) { IMS_PHOTON_VARIANTS_MODE0(IMS_TRY_VARIANT) }
+    else if constexpr (MODE == 1) { IMS_PHOTON_VARIANTS_MODE1(IMS_TRY_VARIANT) }
+    else { IMS_PHOTON_VARIANTS_MODE2(IMS_TRY_VARIANT) }
+#undef IMS_TRY_VARIANT
+    char msg[160];
+    snprintf(msg, sizeof(msg), "no photon kernel <CHAIN %d, PSF %d, LAYOUT 0x%llx> for mode %d", v.chain, v.psf, v.layout, MODE);
+    return set_err(IMS_ERR_UNSUPPORTED, msg);
+}
+
+// f(std::integral_constant<int, NV>) with the vertices per pixel edge as the sensor kernels' template argument: 4, 8, or 0 for
+// the forms that loop over any count
+template <class F>
+static void with_nv(int num_vertices, F&& f)
+{
+    if (num_vertices == 4) f(std::integral_constant<int, 4>{});
+    else if (num_vertices == 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
+// what ims_accumulate_segments / _small / _round ask of the pool and the image they deposit it into
+static int check_pooled_accumulate(const ims_render_params_t* params, const ims_photons_t* pool, const int64_t* pool_start)
+{
+    if (!pool || !pool_start) return set_err(IMS_ERR_ARG, "pool/pool_start is NULL");
+    if (!pool->converted) return set_err(IMS_ERR_ARG, "pool must hold converted photons (ims_shoot_ops_photons with pool->converted = 1)");
+    if (!params->image) return set_err(IMS_ERR_ARG, "image is NULL");
+    if (params->lazy_static) return set_err(IMS_ERR_ARG, "lazy_static parameters (slot 0 holds no state) belong to ims_shoot_accumulate only");
+    return IMS_OK;
+}
+
 extern "C" {
 
 int ims_abi_version(void) { return IMS_ABI_VERSION; }
@@ -3357,42 +3455,13 @@ int ims_last_kernel_ms(float* ms, int* n_launches)
     return IMS_OK;
 }
 
-// the descriptor lists exactly imSim's default photon-op chain (run_ops<1>)
-static bool is_default_chain(const ims_render_params_t* p)
+int ims_photon_kernel_variant(const ims_render_params_t* params, int32_t mode, int32_t* chain, int32_t* psf, uint64_t* layout)
 {
-    static const int32_t kinds[IMS_DEFAULT_CHAIN_LEN] = { IMS_OP_TIME_SAMPLER, IMS_OP_PUPIL_ANNULUS_SAMPLER, IMS_OP_PHOTON_DCR,
-                                                          IMS_OP_RUBIN_DIFFRACTION_OPTICS, IMS_OP_FOCUS_DEPTH, IMS_OP_REFRACTION };
-    if (p->n_ops != IMS_DEFAULT_CHAIN_LEN || !g_tune.chain_kernels) return false;
-    for (int k = 0; k < IMS_DEFAULT_CHAIN_LEN; ++k)
-        if (p->ops[k].kind != kinds[k]) return false;
-    return true;
-}
-
-// 1: radial table then Gaussian (run_psf<1>); 2: phase screens, second-kick table, Gaussian (run_psf<2>: imSim's default
-// AtmosphericPSF); 0: anything else.  (Variant 2 is slower than the component loop at four workgroups per CU -- C3b 36.9 -> 38.6 ms
-// in round 2, 35.2 -> 35.9 ms now -- and faster at the three that launches with phase screens run with (photon_lds_pad):
-// 33.7 -> 33.2 ms.  ims_tuning_t.psf_screens_kernel = 0 takes the loop.)
-// 3: a list with an optical phase screen (IMS_PSF_OPTICAL_SCREEN) in it (run_psf<3>); 4: screens, second kick, optical screen,
-// Gaussian -- AtmosphericPSF with doOpt (run_psf<4>), taken under the same switches as variant 2.  Lists without the component
-// never reach a kernel compiled for it, and the other way round (a missing kernel is not replaced by another).
-static bool has_optical_screen(const ims_render_params_t* p)
-{
-    for (int c = 0; c < p->n_psf; ++c)
-        if (p->psf[c].kind == IMS_PSF_OPTICAL_SCREEN) return true;
-    return false;
-}
-static int psf_variant(const ims_render_params_t* p)
-{
-    if (has_optical_screen(p)) {
-        if (g_tune.chain_kernels && g_tune.psf_screens_kernel && p->n_psf == 4 && p->psf[0].kind == IMS_PSF_SCREENS &&
-            p->psf[1].kind == IMS_PSF_RADIAL && p->psf[2].kind == IMS_PSF_OPTICAL_SCREEN && p->psf[3].kind == IMS_PSF_GAUSSIAN) return 4;
-        return 3;
-    }
-    if (!g_tune.chain_kernels) return 0;
-    if (p->n_psf == 2 && p->psf[0].kind == IMS_PSF_RADIAL && p->psf[1].kind == IMS_PSF_GAUSSIAN) return 1;
-    if (g_tune.psf_screens_kernel && p->n_psf == 3 && p->psf[0].kind == IMS_PSF_SCREENS && p->psf[1].kind == IMS_PSF_RADIAL &&
-        p->psf[2].kind == IMS_PSF_GAUSSIAN && p->atm != nullptr) return 2;
-    return 0;
+    if (!params || !chain || !psf || !layout) return set_err(IMS_ERR_ARG, "params / chain / psf / layout is NULL");
+    if (mode < 0 || mode > 2) return set_err(IMS_ERR_ARG, "mode must be 0, 1 or 2");
+    const PhotonVariant v = select_photon_variant(params, mode);
+    *chain = v.chain; *psf = v.psf; *layout = v.layout;
+    return IMS_OK;
 }
 
 int ims_known_optics_layout(uint64_t layout) { return layout == IMS_LAYOUT_RUBIN_LIKE ? 1 : 0; }
@@ -3463,27 +3532,11 @@ int ims_shoot_accumulate(const ims_render_params_t* params_in, void* stream)
     {
         LaunchTimer tm(st, 1);
         const dim3 grid(grid_for_segments(params->n_segments));
-        const int pv = is_default_chain(params) ? psf_variant(params) : -1;
-        const bool lay = pv >= 0 && params->optics_layout == IMS_LAYOUT_RUBIN_LIKE && g_tune.layout_kernels != 0;
-        // lists with an optical phase screen: the straight-line kernel of AtmosphericPSF(doOpt) on the default chain and layout,
-        // else the loops over components, operators and surfaces
-        if (has_optical_screen(params)) {
-            if (params->optics_layout == IMS_LAYOUT_PERTURBED)
-                hipLaunchKernelGGL((k_shoot_accumulate<0, 3, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params);
-            else if (pv == 4 && lay)
-                hipLaunchKernelGGL((k_shoot_accumulate<1, 4, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params);
-            else hipLaunchKernelGGL((k_shoot_accumulate<0, 3>), grid, dim3(256), photon_lds_pad(params), st, *params);
-        } else
-        // a perturbed telescope (include/imsim_hip.h): the loops over the operators and the surfaces, every surface in its frame
-        if (params->optics_layout == IMS_LAYOUT_PERTURBED)
-            hipLaunchKernelGGL((k_shoot_accumulate<0, 0, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params);
-        else if (pv == 2 && lay) hipLaunchKernelGGL((k_shoot_accumulate<1, 2, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params);
-        else if (pv == 2) hipLaunchKernelGGL((k_shoot_accumulate<1, 0>), grid, dim3(256), photon_lds_pad(params), st, *params);
-        else if (pv == 1 && lay) hipLaunchKernelGGL((k_shoot_accumulate<1, 1, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params);
-        else if (pv == 0 && lay) hipLaunchKernelGGL((k_shoot_accumulate<1, 0, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params);
-        else if (pv == 1) hipLaunchKernelGGL((k_shoot_accumulate<1, 1>), grid, dim3(256), photon_lds_pad(params), st, *params);
-        else if (pv == 0) hipLaunchKernelGGL((k_shoot_accumulate<1, 0>), grid, dim3(256), photon_lds_pad(params), st, *params);
-        else hipLaunchKernelGGL((k_shoot_accumulate<0, 0>), grid, dim3(256), photon_lds_pad(params), st, *params);
+        rc = launch_photon_variant<2>(select_photon_variant(params, 2), [&](auto k) {
+            using K = decltype(k);
+            hipLaunchKernelGGL((k_shoot_accumulate<K::chain, K::psf, K::layout>), grid, dim3(256), photon_lds_pad(params), st, *params);
+        });
+        if (rc) return rc;
     }
     HIP_TRY(hipGetLastError());
     if (params->lazy_static) {
@@ -3502,14 +3555,12 @@ int ims_shoot_photons(const ims_render_params_t* params, const int64_t* photon_o
     if (!photon_offset || !pool) return set_err(IMS_ERR_ARG, "photon_offset/pool is NULL");
     if (params->n_segments == 0) return IMS_OK;
     hipStream_t st = (hipStream_t)stream;
-    {
-        if (has_optical_screen(params))
-            hipLaunchKernelGGL((k_shoot_photons<0, 0, 3>), dim3(grid_for_segments(params->n_segments)), dim3(256), 0, st,
-                               *params, photon_offset, *pool);
-        else
-        hipLaunchKernelGGL((k_shoot_photons<0, 0>), dim3(grid_for_segments(params->n_segments)), dim3(256), 0, st,
+    rc = launch_photon_variant<0>(select_photon_variant(params, 0), [&](auto k) {
+        using K = decltype(k);
+        hipLaunchKernelGGL((k_shoot_photons<0, K::chain, K::psf, K::layout>), dim3(grid_for_segments(params->n_segments)), dim3(256), 0, st,
                            *params, photon_offset, *pool);
-    }
+    });
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return IMS_OK;
 }
@@ -3527,35 +3578,18 @@ int ims_shoot_ops_photons(const ims_render_params_t* params, const int64_t* phot
     {
         LaunchTimer tm(st, 2);
         const dim3 grid(grid_for_segments(params->n_segments));
-        const int pv = is_default_chain(params) ? psf_variant(params) : -1;
-        const bool lay = pv >= 0 && params->optics_layout == IMS_LAYOUT_RUBIN_LIKE && g_tune.layout_kernels != 0;
-        const bool pert = params->optics_layout == IMS_LAYOUT_PERTURBED;
-        if (has_optical_screen(params)) {
-            if (pool->converted && pert)
-                hipLaunchKernelGGL((k_shoot_photons<2, 0, 3, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-            else if (pert)
-                hipLaunchKernelGGL((k_shoot_photons<1, 0, 3, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-            else if (pool->converted && pv == 4 && lay)
-                hipLaunchKernelGGL((k_shoot_photons<2, 1, 4, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-            else if (pool->converted) hipLaunchKernelGGL((k_shoot_photons<2, 0, 3>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-            else hipLaunchKernelGGL((k_shoot_photons<1, 0, 3>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-        } else
-        if (pool->converted && pert)
-            hipLaunchKernelGGL((k_shoot_photons<2, 0, 0, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-        else if (pert)
-            hipLaunchKernelGGL((k_shoot_photons<1, 0, 0, IMS_LAYOUT_PERTURBED>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-        else if (pool->converted && pv == 2 && lay)
-            hipLaunchKernelGGL((k_shoot_photons<2, 1, 2, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-        else if (pool->converted && pv == 2)
-            hipLaunchKernelGGL((k_shoot_photons<2, 1, 0>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-        else if (pool->converted && pv == 1 && lay)
-            hipLaunchKernelGGL((k_shoot_photons<2, 1, 1, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-        else if (pool->converted && pv == 0 && lay)
-            hipLaunchKernelGGL((k_shoot_photons<2, 1, 0, IMS_LAYOUT_RUBIN_LIKE>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-        else if (pool->converted && pv == 1) hipLaunchKernelGGL((k_shoot_photons<2, 1, 1>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-        else if (pool->converted && pv == 0) hipLaunchKernelGGL((k_shoot_photons<2, 1, 0>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-        else if (pool->converted) hipLaunchKernelGGL((k_shoot_photons<2, 0>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
-        else hipLaunchKernelGGL((k_shoot_photons<1, 0>), grid, dim3(256), photon_lds_pad(params), st, *params, photon_offset, *pool);
+        const unsigned lds = photon_lds_pad(params);
+        if (pool->converted)
+            rc = launch_photon_variant<2>(select_photon_variant(params, 2), [&](auto k) {
+                using K = decltype(k);
+                hipLaunchKernelGGL((k_shoot_photons<2, K::chain, K::psf, K::layout>), grid, dim3(256), lds, st, *params, photon_offset, *pool);
+            });
+        else
+            rc = launch_photon_variant<1>(select_photon_variant(params, 1), [&](auto k) {
+                using K = decltype(k);
+                hipLaunchKernelGGL((k_shoot_photons<1, K::chain, K::psf, K::layout>), grid, dim3(256), lds, st, *params, photon_offset, *pool);
+            });
+        if (rc) return rc;
     }
     HIP_TRY(hipGetLastError());
     return IMS_OK;
@@ -3565,22 +3599,13 @@ int ims_accumulate_segments(const ims_render_params_t* params, const ims_photons
                             int32_t num_vertices, void* stream)
 {
     int rc = check_params(params);
+    if (!rc) rc = check_pooled_accumulate(params, pool, pool_start);
     if (rc) return rc;
-    if (!pool || !pool_start) return set_err(IMS_ERR_ARG, "pool/pool_start is NULL");
-    if (!pool->converted) return set_err(IMS_ERR_ARG, "pool must hold converted photons (ims_shoot_ops_photons with pool->converted = 1)");
-    if (!params->image) return set_err(IMS_ERR_ARG, "image is NULL");
-    if (params->lazy_static) return set_err(IMS_ERR_ARG, "lazy_static parameters (slot 0 holds no state) belong to ims_shoot_accumulate only");
     if (params->n_segments == 0) return IMS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    {
-        const dim3 grid(grid_for_segments(params->n_segments));
-        if (num_vertices == 4)
-            hipLaunchKernelGGL(k_accumulate_segments<4>, grid, dim3(256), 0, st, *params, *pool, pool_start);
-        else if (num_vertices == 8)
-            hipLaunchKernelGGL(k_accumulate_segments<8>, grid, dim3(256), 0, st, *params, *pool, pool_start);
-        else
-            hipLaunchKernelGGL(k_accumulate_segments<0>, grid, dim3(256), 0, st, *params, *pool, pool_start);
-    }
+    const dim3 grid(grid_for_segments(params->n_segments));
+    with_nv(num_vertices, [&](auto nv) {
+        hipLaunchKernelGGL(k_accumulate_segments<decltype(nv)::value>, grid, dim3(256), 0, (hipStream_t)stream, *params, *pool, pool_start);
+    });
     HIP_TRY(hipGetLastError());
     return IMS_OK;
 }
@@ -3590,17 +3615,15 @@ int ims_accumulate_small(const ims_render_params_t* params, const ims_photons_t*
 {
     if (!params) return set_err(IMS_ERR_ARG, "params is NULL");
     if (!params->objects || !params->image) return set_err(IMS_ERR_ARG, "objects/image is NULL");
-    if (!pool || !pool_start) return set_err(IMS_ERR_ARG, "pool/pool_start is NULL");
-    if (!pool->converted) return set_err(IMS_ERR_ARG, "pool must hold converted photons (ims_shoot_ops_photons with pool->converted = 1)");
-    if (params->lazy_static) return set_err(IMS_ERR_ARG, "lazy_static parameters (slot 0 holds no state) belong to ims_shoot_accumulate only");
+    const int rc = check_pooled_accumulate(params, pool, pool_start);
+    if (rc) return rc;
     if (params->n_objects <= 0) return IMS_OK;
     const int64_t blocks = (params->n_objects + 3) / 4;
     if (blocks > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "too many objects for one launch");
     const dim3 grid((unsigned)blocks);
-    hipStream_t st = (hipStream_t)stream;
-    if (num_vertices == 4) hipLaunchKernelGGL(k_accumulate_small<4>, grid, dim3(256), 0, st, *params, *pool, pool_start);
-    else if (num_vertices == 8) hipLaunchKernelGGL(k_accumulate_small<8>, grid, dim3(256), 0, st, *params, *pool, pool_start);
-    else hipLaunchKernelGGL(k_accumulate_small<0>, grid, dim3(256), 0, st, *params, *pool, pool_start);
+    with_nv(num_vertices, [&](auto nv) {
+        hipLaunchKernelGGL(k_accumulate_small<decltype(nv)::value>, grid, dim3(256), 0, (hipStream_t)stream, *params, *pool, pool_start);
+    });
     HIP_TRY(hipGetLastError());
     return IMS_OK;
 }
@@ -3610,8 +3633,8 @@ int ims_accumulate_round(const ims_render_params_t* params, const ims_photons_t*
 {
     if (!params) return set_err(IMS_ERR_ARG, "params is NULL");
     if (!params->objects || !params->image) return set_err(IMS_ERR_ARG, "objects/image is NULL");
-    if (!pool || !pool_start) return set_err(IMS_ERR_ARG, "pool/pool_start is NULL");
-    if (!pool->converted) return set_err(IMS_ERR_ARG, "pool must hold converted photons (ims_shoot_ops_photons with pool->converted = 1)");
+    const int rc = check_pooled_accumulate(params, pool, pool_start);
+    if (rc) return rc;
     if (round < 0 || nrecalc <= 0) return set_err(IMS_ERR_ARG, "round must be >= 0 and nrecalc positive");
     if (n_active < 0 || n_active > params->n_objects) return set_err(IMS_ERR_ARG, "n_active out of range");
     if (n_active == 0) return IMS_OK;
@@ -3623,12 +3646,10 @@ int ims_accumulate_round(const ims_render_params_t* params, const ims_photons_t*
     const dim3 grid((unsigned)(n_active * segs));
     const int64_t first = (int64_t)round * nrecalc;
     LaunchTimer tm((hipStream_t)stream, 4);
-    if (num_vertices == 4)
-        hipLaunchKernelGGL(k_accumulate_round<4>, grid, dim3(256), 0, (hipStream_t)stream, *params, *pool, pool_start, first, nrecalc, segs);
-    else if (num_vertices == 8)
-        hipLaunchKernelGGL(k_accumulate_round<8>, grid, dim3(256), 0, (hipStream_t)stream, *params, *pool, pool_start, first, nrecalc, segs);
-    else
-        hipLaunchKernelGGL(k_accumulate_round<0>, grid, dim3(256), 0, (hipStream_t)stream, *params, *pool, pool_start, first, nrecalc, segs);
+    with_nv(num_vertices, [&](auto nv) {
+        hipLaunchKernelGGL(k_accumulate_round<decltype(nv)::value>, grid, dim3(256), 0, (hipStream_t)stream, *params, *pool, pool_start, first,
+                           nrecalc, segs);
+    });
     HIP_TRY(hipGetLastError());
     return IMS_OK;
 }
@@ -3837,30 +3858,22 @@ static int update_distortions_impl(const ims_sensor_t* sensor_dev, const ims_sen
     // one star), the SGPR form where a launch is throughput work beside the photon kernels (its waves sleep on the scalar
     // cache instead of pulling 10 KB of table through LDS per tile: C3 25.0 against 25.9 ms): the tile count decides.
     const bool dpp = sensor_host && sensor_host->bf_dl != nullptr && g_tune.upd_dpp && n_tiles <= g_tune.upd_dpp_max;
-    if (q == 3 && nV == 4 && dpp)
-        hipLaunchKernelGGL((k_update_distortions_q3<4, true>), dim3((unsigned)n_tiles), dim3(256), 0, st, sensor_dev, first_slot,
-                           n_slots, tile_prefix_dev, changed_dev, tag, sensor_host->bf_dl);
-    else if (q == 3 && nV == 8 && dpp)
-        hipLaunchKernelGGL((k_update_distortions_q3<8, true>), dim3((unsigned)n_tiles), dim3(256), 0, st, sensor_dev, first_slot,
-                           n_slots, tile_prefix_dev, changed_dev, tag, sensor_host->bf_dl);
-    else if (q == 3 && nV == 4)
-        hipLaunchKernelGGL(k_update_distortions_q3<4>, dim3((unsigned)n_tiles), dim3(256), 0, st, sensor_dev, first_slot,
-                           n_slots, tile_prefix_dev, changed_dev, tag, sensor_host->bf_dl);
-    else if (q == 3 && nV == 8)
-        hipLaunchKernelGGL(k_update_distortions_q3<8>, dim3((unsigned)n_tiles), dim3(256), 0, st, sensor_dev, first_slot,
-                           n_slots, tile_prefix_dev, changed_dev, tag, sensor_host->bf_dl);
-    else
-        hipLaunchKernelGGL(k_update_distortions, dim3((unsigned)n_tiles), dim3(256), 0, st, sensor_dev, first_slot, n_slots,
-                           tile_prefix_dev, changed_dev, tag);
-    if (nV == 4)
-        hipLaunchKernelGGL(k_refresh_changed<4>, dim3((unsigned)n_tiles), dim3(256), 0, st, sensor_dev, first_slot, n_slots,
-                           tile_prefix_dev, (const unsigned char*)changed_dev, tag, fold_image);
-    else if (nV == 8)
-        hipLaunchKernelGGL(k_refresh_changed<8>, dim3((unsigned)n_tiles), dim3(256), 0, st, sensor_dev, first_slot, n_slots,
-                           tile_prefix_dev, (const unsigned char*)changed_dev, tag, fold_image);
-    else
-        hipLaunchKernelGGL(k_refresh_changed<0>, dim3((unsigned)n_tiles), dim3(256), 0, st, sensor_dev, first_slot, n_slots,
-                           tile_prefix_dev, (const unsigned char*)changed_dev, tag, fold_image);
+    const dim3 grid((unsigned)n_tiles);
+    with_nv(nV, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        if constexpr (NV != 0) {                                                      // (the q3 update has no form for other counts)
+            if (q == 3) {
+                hipLaunchKernelGGL((dpp ? k_update_distortions_q3<NV, true> : k_update_distortions_q3<NV, false>), grid, dim3(256), 0, st,
+                                   sensor_dev, first_slot, n_slots, tile_prefix_dev, changed_dev, tag, sensor_host->bf_dl);
+                return;
+            }
+        }
+        hipLaunchKernelGGL(k_update_distortions, grid, dim3(256), 0, st, sensor_dev, first_slot, n_slots, tile_prefix_dev, changed_dev, tag);
+    });
+    with_nv(nV, [&](auto nv) {
+        hipLaunchKernelGGL(k_refresh_changed<decltype(nv)::value>, grid, dim3(256), 0, st, sensor_dev, first_slot, n_slots, tile_prefix_dev,
+                           (const unsigned char*)changed_dev, tag, fold_image);
+    });
     HIP_TRY(hipGetLastError());
     return IMS_OK;
 }

@@ -501,6 +501,11 @@ int  ims_device_info(int device, int* n_cu, int* n_xcd, int64_t* lds_bytes, int6
 
 /* 1 when the library holds kernels specialised for this optics layout (ims_render_params_t.optics_layout) */
 int  ims_known_optics_layout(uint64_t layout);
+/* Which instantiation k_shoot_accumulate<CHAIN, PSF, LAYOUT> / k_shoot_photons<MODE, CHAIN, PSF, LAYOUT> a launch with these
+ * parameters gets under the current tuning block; launches nothing (host code only).  mode: 0 ims_shoot_photons, 1
+ * ims_shoot_ops_photons on a pool that is not converted, 2 the same on a converted pool and ims_shoot_accumulate.  Reads only n_ops,
+ * ops[].kind, n_psf, psf[].kind, atm and optics_layout.  IMS_ERR_ARG for a NULL argument or another mode. */
+int  ims_photon_kernel_variant(const ims_render_params_t* params, int32_t mode, int32_t* chain, int32_t* psf, uint64_t* layout);
 
 /* ---- tuning: which of its equivalent forms the library launches ----
  * Every alternative below computes the same bits by another route (the parity tests run under each of them); the defaults are
@@ -1123,7 +1128,7 @@ int  ims_image_to_float(const double* src, float* dst, int64_t n, void* stream);
 
 /* ---- timing of the dominant kernel ----
  * After ims_enable_timing(which) every launch of the selected kernel is bracketed by a hipEvent pair on its
- * stream: which = 1 k_shoot_accumulate (ims_shoot_accumulate), 2 k_shoot_photons<true> (ims_shoot_ops_photons),
+ * stream: which = 1 k_shoot_accumulate (ims_shoot_accumulate), 2 k_shoot_photons<MODE 1 or 2> (ims_shoot_ops_photons),
  * 4 k_accumulate_round (the pixel search of a brighter-fatter round), 0 = off.  ims_last_kernel_ms returns the SUM of their durations and their count since the last query
  * (and resets the accumulation). */
 int  ims_last_kernel_ms(float* ms, int* n_launches);
