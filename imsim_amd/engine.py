@@ -66,7 +66,7 @@ class Scene:
     radial_cdf: Optional[np.ndarray] = None
     image_profiles: Optional[list] = None        # 2-D arrays [ny][nx] sampled by IMS_PROF_IMAGE objects (FITS stamps)
     image_interpolant: str = "quintic"           # x_interpolant of those images: GalSim's default, or "nearest"
-    sed_tables: Optional[np.ndarray] = None      # [n][n_pts] inverse CDFs uniform in u
+    sed_tables: Optional[np.ndarray] = None      # [n][n_pts] inverse CDFs uniform in u; or a torch f64 tensor on the renderer's device
     ratio_tables: Optional[np.ndarray] = None    # [n][n_pts] uniform in wavelength
     ratio_wl_min: float = 0.0
     ratio_wl_step: float = 1.0
@@ -635,10 +635,24 @@ class BoundScene:
             _, P.radial.guide = mem.put(guide, np.int32)
             P.radial.n_guide = n_guide
         if scene.sed_tables is not None:
-            t = np.atleast_2d(scene.sed_tables)
+            t = scene.sed_tables
+            on_device = not isinstance(t, np.ndarray) and hasattr(t, "data_ptr")      # a torch tensor (sed.object_spectra_hip)
+            if on_device and not isinstance(mem, DeviceMem):
+                t, on_device = t.cpu().numpy(), False                                  # the checker reads a host copy
+            if on_device:
+                # the kernels read it where it lies: nothing goes through the host
+                index = mem.device.index if mem.device.index is not None else mem.torch.cuda.current_device()
+                if t.device.type != mem.device.type or t.device.index != index or t.dtype != mem.torch.float64 or t.dim() != 2:
+                    raise ValueError(f"Scene.sed_tables: a device tensor must be f64 [n][n_pts] on {mem.device} "
+                                     f"(got {t.dtype} {tuple(t.shape)} on {t.device})")
+                t = t.contiguous()
+                mem.keep.append(t)
+                P.sed.val = t.data_ptr()
+            else:
+                t = np.atleast_2d(t)
+                _, P.sed.val = mem.put(t, np.float64)
             P.sed.n_tables, P.sed.n_pts = t.shape
             P.sed.arg_min, P.sed.arg_step = 0.0, 1.0 / (t.shape[1] - 1)
-            _, P.sed.val = mem.put(t, np.float64)
         if scene.ratio_tables is not None:
             t = np.atleast_2d(scene.ratio_tables)
             P.ratio.n_tables, P.ratio.n_pts = t.shape

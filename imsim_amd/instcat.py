@@ -254,11 +254,15 @@ def parse_dust(params):
 
 
 def to_catalog(parsed, img_wcs, xsize, ysize, bandpass_integral, exptime, pupil_area=RUBIN_AREA, edge_pix=100,
-               sort_mag=True, flip_g2=True, sed_dir=None, inst_dir=None, bandpass=None, sed_points=257):
+               sort_mag=True, flip_g2=True, sed_dir=None, inst_dir=None, bandpass=None, sed_points=257, sed_device=None):
     """Cull to the CCD (+- edge_pix, instcat.py:243-259), compute nominal fluxes and the profile
     geometry (instcat.py:498-527, :433-444, :569-573) -> the catalog dict build_object_table takes.
     point, sersic2d, knots, streak and FITS-image objects reach the kernels; a FITS-image object whose file is
-    missing is dropped with the count in n_dropped_unsupported."""
+    missing is dropped with the count in n_dropped_unsupported.
+    sed_device: a torch device -- the SEDs are integrated through the bandpass there (sed.object_spectra_hip) and
+    cat["sed_tables"] is a device tensor [1 + found objects][sed_points] whose row 0 is left for the caller's flat fallback
+    table (sed_table indexes it as it stands); None: on the host, cat["sed_tables"] a numpy array of the found objects' rows,
+    to go behind the fallback."""
     from . import wcs as wcsmod
     vec = wcsmod.unit_vector(parsed["ra"], parsed["dec"]).T
     x, y = wcsmod.tansip_vec_to_pix(img_wcs, vec)
@@ -281,12 +285,23 @@ def to_catalog(parsed, img_wcs, xsize, ysize, bandpass_integral, exptime, pupil_
         names = np.array([parsed["sed"][i][0] for i in idx], dtype=object)
         z = np.array([parsed["sed"][i][1] for i in idx], dtype=np.float64)
         d = parsed["dust"][idx] if "dust" in parsed else np.tile([0.0, 3.1, 0.0, 3.1], (len(idx), 1))
-        f0, tabs, missing = sedmod.object_spectra(names, z, d[:, 2], d[:, 3], bandpass[0], bandpass[1],
-                                                  sedmod.SedLibrary(sed_dir, inst_dir), n_pts=sed_points)
+        library = sedmod.SedLibrary(sed_dir, inst_dir)
+        if sed_device is None:
+            f0, tabs, missing = sedmod.object_spectra(names, z, d[:, 2], d[:, 3], bandpass[0], bandpass[1], library, n_pts=sed_points)
+        else:
+            f0, tabs, missing = sedmod.object_spectra_hip(names, z, d[:, 2], d[:, 3], bandpass[0], bandpass[1], library,
+                                                          n_pts=sed_points, device=sed_device, lead_rows=1)
         found = f0 >= 0.0
         flux = np.where(found, f0 * np.exp(-0.9210340371976184 * parsed["magnorm"][idx]) * pupil_area * exptime, flux)
         if found.any():
-            sed_tables = tabs[found]
+            if sed_device is None:
+                sed_tables = tabs[found]
+            elif found.all():
+                sed_tables = tabs
+            else:                                                       # the rows of the found objects, gathered on the device
+                import torch
+                rows = np.concatenate([[0], 1 + np.flatnonzero(found)])
+                sed_tables = tabs.index_select(0, torch.from_numpy(rows).to(tabs.device))
             sed_table[found] = 1 + np.arange(int(found.sum()))          # table 0 stays the flat fallback
     objtype = parsed["objtype"][idx]
     n = parsed["n"][idx]

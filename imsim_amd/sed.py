@@ -58,9 +58,9 @@ class SED:
         return SED(self.wave, self.fphotons, z)
 
 
-def ccm89(wave_nm, rv=3.1):
-    """A(lambda) / A(V) of Cardelli, Clayton & Mathis (1989) with O'Donnell (1994) in the optical; x = 1 / lambda [1/um]
-    clipped to the curve's range 0.3 .. 10."""
+def ccm89_terms(wave_nm):
+    """(a, b) of Cardelli, Clayton & Mathis (1989) with O'Donnell (1994) in the optical: A(lambda) / A(V) = a + b / R_v;
+    x = 1 / lambda [1/um] clipped to the curve's range 0.3 .. 10."""
     x = np.clip(1.0e3 / np.asarray(wave_nm, dtype=np.float64), 0.3, 10.0)
     a = np.zeros_like(x)
     b = np.zeros_like(x)
@@ -81,6 +81,12 @@ def ccm89(wave_nm, rv=3.1):
     yf = x[fuv] - 8.0
     a[fuv] = -1.073 + yf * (-0.628 + yf * (0.137 - 0.070 * yf))
     b[fuv] = 13.670 + yf * (4.257 + yf * (-0.420 + 0.374 * yf))
+    return a, b
+
+
+def ccm89(wave_nm, rv=3.1):
+    """A(lambda) / A(V) of that curve for one R_v"""
+    a, b = ccm89_terms(wave_nm)
     return a + b / rv
 
 
@@ -158,3 +164,89 @@ def object_spectra(names, redshift, mw_av, mw_rv, bandpass_wave, bandpass_thr, l
                 keep = np.concatenate([[True], np.diff(c) > 0])
                 tables[i] = np.interp(u, c[keep], grid[keep])
     return flux, tables, sorted(missing)
+
+
+def band_grid(bandpass_wave, bandpass_thr, step=0.5):
+    """The grid object_spectra integrates on and the throughput on it: (lo, hi, grid, thr)"""
+    lo, hi = float(bandpass_wave[0]), float(bandpass_wave[-1])
+    grid = np.arange(lo, hi + 0.5 * step, step)
+    grid[-1] = min(grid[-1], hi)
+    return lo, hi, grid, np.interp(grid, bandpass_wave, bandpass_thr, left=0.0, right=0.0)
+
+
+def pack_library(library, names):
+    """The SEDs a list of objects names, packed for ims_object_spectra.
+
+    names [n] SED file names.  Returns (wave, fphotons: the rest wavelengths [nm] and photons / nm / cm^2 / s of the SEDs that
+    were found, one behind the other in the order of their sorted names, normalised as SedLibrary.get hands them out,
+    offset [n_sed + 1] int64: SED k is wave[offset[k] : offset[k + 1]],
+    sed_id [n] int32: the SED of every object, -1 where the file was not found,
+    missing: the sorted names of those files)."""
+    names = np.asarray(names, dtype=object).tolist()
+    index, missing, waves, fphot, offset = {}, [], [], [], [0]
+    for name in sorted(set(names)):
+        sed = library.get(name)
+        if sed is None:
+            missing.append(name)
+            index[name] = -1
+            continue
+        index[name] = len(waves)
+        waves.append(sed.wave)
+        fphot.append(sed.fphotons)
+        offset.append(offset[-1] + len(sed.wave))
+    sed_id = np.fromiter((index[name] for name in names), dtype=np.int32, count=len(names))
+    wave = np.concatenate(waves) if waves else np.zeros(0)
+    fphotons = np.concatenate(fphot) if fphot else np.zeros(0)
+    return wave, fphotons, np.asarray(offset, dtype=np.int64), sed_id, missing
+
+
+def object_spectra_hip(names, redshift, mw_av, mw_rv, bandpass_wave, bandpass_thr, library, n_pts=257, step=0.5, device="cuda:0",
+                       lead_rows=0, out=None, timing=None):
+    """object_spectra on the GPU (ims_object_spectra): the same arguments and the same contract, except that
+    (flux [n]: numpy, one copy from the device,
+     tables [lead_rows + n][n_pts]: a torch f64 tensor that STAYS on `device`; its first lead_rows rows are the caller's (zero
+     here, or what `out` -- a contiguous f64 tensor of that shape on the device -- held: they are not touched),
+     missing).
+    The sums are formed in another order than the host's, so fluxes and tables agree with object_spectra to rounding (a few
+    1e-13 relative in the flux), not bit for bit.  There is no host fallback: without the library or a GPU this raises.
+    timing: a dict that receives "launch_ms", the time of the launch alone between two events (tools/sed_timing.py)."""
+    import torch
+    from . import _abi
+    lib = _abi.load()
+    dev = torch.device(device)
+    n = len(names)
+    lo, hi, grid, thr = band_grid(bandpass_wave, bandpass_thr, step)
+    ext_a, ext_b = ccm89_terms(grid)
+    wave, fphotons, offset, sed_id, missing = pack_library(library, names)
+    n_sed = len(offset) - 1
+    f64 = np.concatenate([grid, thr, ext_a, ext_b, wave, fphotons, np.asarray(redshift, dtype=np.float64),
+                          np.asarray(mw_av, dtype=np.float64), np.asarray(mw_rv, dtype=np.float64)])
+    if len(f64) != 4 * len(grid) + 2 * len(wave) + 3 * n:
+        raise ValueError("object_spectra_hip: redshift, mw_av and mw_rv need one value per name")
+    d64 = torch.from_numpy(f64).to(dev)
+    parts = torch.split(d64, [len(grid)] * 4 + [len(wave)] * 2 + [n] * 3)
+    d_off = torch.from_numpy(offset).to(dev)
+    d_id = torch.from_numpy(sed_id).to(dev)
+    if out is None:
+        tables = torch.zeros((lead_rows + n, n_pts), dtype=torch.float64, device=dev)
+    else:
+        tables = out
+        if (tables.device != d64.device or tables.dtype != torch.float64 or tuple(tables.shape) != (lead_rows + n, n_pts)
+                or not tables.is_contiguous()):
+            raise ValueError(f"object_spectra_hip: out must be a contiguous f64 tensor of shape {(lead_rows + n, n_pts)} on {dev}")
+    flux = torch.empty(n, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if timing is not None:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+        _abi.check(lib.ims_object_spectra(parts[0].data_ptr(), parts[1].data_ptr(), parts[2].data_ptr(), parts[3].data_ptr(), len(grid), hi,
+                                          parts[4].data_ptr(), parts[5].data_ptr(), d_off.data_ptr(), n_sed, d_id.data_ptr(),
+                                          parts[6].data_ptr(), parts[7].data_ptr(), parts[8].data_ptr(), n, n_pts, flux.data_ptr(),
+                                          tables.data_ptr(), lead_rows, stream), "ims_object_spectra")
+        if timing is not None:
+            ev[1].record()
+    flux = flux.cpu().numpy()
+    if timing is not None:
+        timing["launch_ms"] = ev[0].elapsed_time(ev[1])
+    return flux, tables, missing

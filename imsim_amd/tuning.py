@@ -60,6 +60,10 @@ KNOWN = {
     "IMS_POOL_SMALL_MAX": ("64", "per-batch shares up to this many photons go through ims_accumulate_small"),
     "IMS_POOL_SPATIAL": ("1", "shoot table of pooling mode in spatial order"),
     "IMS_FFT_TORCH": ("0", "inverse transforms of the FFT branch through torch.fft instead of ims_fft_inverse (the checker)"),
+    "IMS_SED_DEVICE": ("0", "config.Process: 1 = the per-object SEDs of an instance catalog are integrated through the bandpass on the GPU "
+                            "(ims_object_spectra; the wavelength tables never leave the device); 0 = sed.object_spectra on the host.  Off by "
+                            "default: the device tables agree with the host's to rounding, not bit for bit, so images of SED catalogs would "
+                            "change their bits"),
     "IMS_EXCHANGE_SINGLE_RANK": ("0", "run the exchanges of a one-rank process group as self-exchanges"),
     # -- focal plane --
     "IMS_FOCAL_STREAMS": ("1", "four plan streams by role for all CCDs of a device; 0 = a set per renderer"),
