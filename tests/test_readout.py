@@ -10,18 +10,64 @@ import pytest
 
 from imsim_amd import _abi, camera, fits_io, readout
 from oracle import orc_loader
+from readout_ref import BLEED_CASES, small_ccd
 
-GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "readout_golden.npz"))
+GOLD_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "readout_golden.npz")
+GOLD = np.load(GOLD_PATH)
 
 
-def small_ccd(seg=(12, 20), raw=(20, 26), prescan=3, vendor="E2V", xtalk=True):
-    """a CCD with the LSSTCam segment topology at toy size"""
-    old = camera.SEGMENT[vendor]
-    camera.SEGMENT[vendor] = dict(seg=seg, raw=raw, prescan=prescan)
-    try:
-        return camera.make_ccd("R22_S11" if vendor == "E2V" else "R01_S00", xtalk=xtalk)
-    finally:
-        camera.SEGMENT[vendor] = old
+# the vectors that were there before the shape cases (BLEED_CASES) were added: the regenerated file holds the same bytes
+GOLD_PINNED = {"chan_in": "55f8b346472b3e62", "chan_out": "8d6e737df0faffc1", "img_in": "5f94d410acc59736",
+               "img_midline": "8b8e57b9d52587e6", "img_nomidline": "f0938ce9c250f6e8", "full_well": "f088acafbda82c98",
+               "neg_in": "55f9a19c4ed3c9a7", "neg_fw": "3844007c3a0c1182", "neg_out": "6ecdd8afc4fcdb2e",
+               "neg_out_native": "ced6f781632fb7ce", "cte_64_1e-6": "1caa309851af925c", "cte_64_1e-3": "a834af9b6eb6537e",
+               "cte_40_1e-2_nt5": "9e1ba450bc4c1c07"}
+
+
+def test_golden_file_keeps_its_earlier_vectors():
+    import hashlib
+    for key, digest in GOLD_PINNED.items():
+        assert hashlib.sha256(np.ascontiguousarray(GOLD[key]).tobytes()).hexdigest()[:16] == digest, key
+    assert set(GOLD.files) == set(GOLD_PINNED) | {f"{c}_{k}" for c in BLEED_CASES for k in ("in", "midline", "nomidline")}
+    assert os.path.getsize(GOLD_PATH) < 200_000
+
+
+@pytest.mark.parametrize("case", BLEED_CASES)
+def test_bleed_shape_cases_match_reference(case):
+    """the oracle against the reference's bleed_trails.py where the device kernels can go wrong: an odd number of rows
+    (unequal halves), channels shorter than eight rows, more than 256 channels, nothing / everything saturated, a pixel
+    exactly at full well, a negative pixel beside a run"""
+    fw = float(GOLD["full_well"])
+    src = GOLD[f"{case}_in"]
+    ny = src.shape[0]
+    for key, mid in (("midline", True), ("nomidline", False)):
+        out = orc_loader.bleed_eimage(src, fw, midline_stop=mid)
+        assert np.array_equal(out, GOLD[f"{case}_{key}"]), (case, key)
+        assert out.max() <= fw and out.sum() <= src.sum()
+    mid, nomid = GOLD[f"{case}_midline"], GOLD[f"{case}_nomidline"]
+    if case == "unsat":
+        assert (src <= fw).all() and (src == fw).any() and np.array_equal(mid, src) and np.array_equal(nomid, src)
+    elif case == "allsat":
+        assert (src > fw).all() and (mid == fw).all() and (nomid == fw).all()
+    else:
+        assert not np.array_equal(mid, src) and not np.array_equal(mid, nomid)      # it bleeds, and the stop matters
+    if case == "odd":
+        ymid = ny // 2
+        assert ny % 2 == 1 and ymid == 48
+        # the run that ends at row 47 grows downwards only with the stop and both ways without it; the reverse at row 48
+        assert mid[48, 2] == src[48, 2] and nomid[48, 2] == fw and mid[47, 5] == src[47, 5] and nomid[47, 5] == fw
+        # the straddling run is two runs with the stop, and each half keeps its own charge
+        assert (src[46:51, 8] > fw).all() and not np.array_equal(mid[:, 8], nomid[:, 8])
+        assert mid[:48, 8].sum() == src[:48, 8].sum() and nomid[:48, 8].sum() != src[:48, 8].sum()
+        assert mid[1, 11] > src[1, 11] and mid[95, 14] > src[95, 14] and mid[95, 17] > src[95, 17] and mid[1, 17] > src[1, 17]
+    if case == "short":
+        assert ny < 8
+    if case.startswith("wide"):
+        nx = src.shape[1]
+        assert nx > 256 and all((src[:ny // 2, x] > fw).any() and (src[ny // 2:, x] > fw).any() for x in (0, 255, 256, nx - 1))
+    if case == "edge":
+        assert src[5, 0] == fw and src[6, 0] == fw + 1 and nomid[5, 0] == fw and nomid[6, 0] == fw and nomid[7, 0] == src[7, 0] + 1
+        assert src[4, 2] < 0 and nomid[4, 2] == fw and src[8, 3] < 0 and nomid[8, 3] > 0
 
 
 def test_bleed_channel_matches_reference():
