@@ -165,8 +165,19 @@ constexpr int CT = 32;
 // charge marks of every tile of every region afterwards (k_build_active_j: 13 - 32 us of every round of a joint run).
 struct JointAcc;
 struct JointRound;
+constexpr int IMS_JOINT_MAX = 64;          // chains of one joint launch (JOINT rounds, below)
+constexpr int ENTRY_CHAIN_BITS = 6, ENTRY_SLOT_BITS = 26, ENTRY_TILE_BITS = 32;     // a tile-list entry: chain << 58 | slot of the class << 32 | tile
+static_assert(ENTRY_CHAIN_BITS + ENTRY_SLOT_BITS + ENTRY_TILE_BITS == 64 && IMS_JOINT_MAX <= (1 << ENTRY_CHAIN_BITS), "chain field too narrow");
+__device__ __forceinline__ unsigned long long pack_tile_entry(int chain, int slot, int tile)
+{
+    return ((unsigned long long)chain << (64 - ENTRY_CHAIN_BITS)) | ((unsigned long long)(unsigned int)slot << ENTRY_TILE_BITS) | (unsigned int)tile;
+}
+__device__ __forceinline__ void unpack_tile_entry(unsigned long long e, int& chain, int& slot, int& tile)
+{
+    chain = (int)(e >> (64 - ENTRY_CHAIN_BITS)); slot = (int)((e >> ENTRY_TILE_BITS) & ((1u << ENTRY_SLOT_BITS) - 1u)); tile = (int)(e & 0xFFFFFFFFu);
+}
 struct TileLister {
-    unsigned long long* list = nullptr; // entries: chain << 58 | slot of the class << 32 | tile of the slot; NULL: no listing (the default)
+    unsigned long long* list = nullptr; // entries: pack_tile_entry; NULL: no listing (the default)
     int* count = nullptr;               // entries so far (this round's parity)
     const JointAcc* J = nullptr;        // per chain: tile words, tiles before each slot of the class, the class's first slot
     const JointRound* R = nullptr;      // per chain: tiles of the regions that go on after this round (only those are updated)
@@ -234,7 +245,7 @@ __device__ __forceinline__ void list_tiles_in_reach(const ChargeTile& ct, int di
             if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == L.round_word) continue;
             if (atomicExch(w, L.round_word) == L.round_word) continue;
             const int k = atomicAdd(L.count, 1);
-            L.list[k] = ((unsigned long long)L.chain << 58) | ((unsigned long long)(unsigned int)C.lo << 32) | (unsigned int)t;
+            L.list[k] = pack_tile_entry(L.chain, C.lo, t);
         }
 }
 
@@ -324,7 +335,7 @@ __device__ __forceinline__ void tile_flush(float* tile, const ChargeTile& ct, co
         if (threadIdx.x == 0) base_new = atomicAdd(L.count, n_new);
         __syncthreads();
         if ((int)threadIdx.x < n_new)
-            L.list[base_new + threadIdx.x] = ((unsigned long long)L.chain << 58) | ((unsigned long long)(unsigned int)C.lo << 32) | (unsigned int)new_tile[threadIdx.x];
+            L.list[base_new + threadIdx.x] = pack_tile_entry(L.chain, C.lo, new_tile[threadIdx.x]);
     }
 }
 
@@ -670,6 +681,16 @@ __global__ __launch_bounds__(256, (NV == 8) ? 2 : 5) void k_accumulate_small(con
     }
 }
 
+// the round's photons [j0, j_end) of object oi that the object's workgroup `seg` searches (wg photons each); false: none
+__device__ __forceinline__ bool round_window(const ims_render_params_t& P, int64_t oi, int64_t seg, int wg, int64_t first, int32_t nrecalc, int64_t& j0, int64_t& j_end)
+{
+    j0 = first + seg * wg;
+    j_end = first + nrecalc;
+    const int64_t n = P.objects[oi].n_phot;
+    if (j_end > n) j_end = n;
+    return j0 < j_end;
+}
+
 // The same for round `round` of a chain class whose table holds the objects' FULL photon counts: the round covers the
 // photons [round * nrecalc, (round + 1) * nrecalc) of every object, `segs` = ceil(nrecalc / 256) workgroups per object;
 // the first n_active rows (sorted by photon count, brightest first) are the objects that reach this round.
@@ -683,11 +704,8 @@ __global__ __launch_bounds__(WG, (NV == 8) ? 2 : 4) void k_accumulate_round(cons
     PROBE(0);
     PROBE_WG(0, 0);
     const int64_t oi = blockIdx.x / segs;
-    const int64_t j0 = round_first + (int64_t)(blockIdx.x % segs) * WG;
-    int64_t j_end = round_first + nrecalc;
-    const int64_t n = P.objects[oi].n_phot;
-    if (j_end > n) j_end = n;
-    if (j0 >= j_end) return;
+    int64_t j0, j_end;
+    if (!round_window(P, oi, (int64_t)(blockIdx.x % segs), WG, round_first, nrecalc, j0, j_end)) return;
     accumulate_segment<NV, WG>(P, pool, pool_start, oi, j0, j_end);
 }
 
@@ -707,24 +725,28 @@ struct RoundArgs {
     int32_t track_static_delta, pad;
 };
 
+// ArgsPtr: the kernel's own argument block, or (joint launches) an entry of a table read through the constant address space
+template <class ArgsPtr>
+__device__ __forceinline__ void unpack_round_args(ArgsPtr a, ims_render_params_t& P, ims_photons_t& pool)
+{
+    P.objects = a->objects; P.sensor = a->sensor; P.image = a->image; P.realized_flux = a->realized_flux;
+    P.nx = a->nx; P.ny = a->ny; P.xmin = a->xmin; P.ymin = a->ymin;
+    P.bf_tag = a->bf_tag; P.bf_slot_shift = a->bf_slot_shift; P.track_static_delta = a->track_static_delta;
+    pool.x = const_cast<double*>(a->px); pool.y = const_cast<double*>(a->py); pool.flux = const_cast<double*>(a->pflux);
+    pool.dxdz = const_cast<double*>(a->pz);
+}
+
 template <int NV, int WG = 256>
 __global__ __launch_bounds__(WG, (NV == 8) ? 2 : 4) void k_accumulate_round_c(const RoundArgs a, const int64_t* __restrict__ pool_start,
                                                           int64_t round_first, int32_t nrecalc, int32_t segs)
 {
     ims_render_params_t P;
-    P.objects = a.objects; P.sensor = a.sensor; P.image = a.image; P.realized_flux = a.realized_flux;
-    P.nx = a.nx; P.ny = a.ny; P.xmin = a.xmin; P.ymin = a.ymin;
-    P.bf_tag = a.bf_tag; P.bf_slot_shift = a.bf_slot_shift; P.track_static_delta = a.track_static_delta;
     ims_photons_t pool;
-    pool.x = const_cast<double*>(a.px); pool.y = const_cast<double*>(a.py); pool.flux = const_cast<double*>(a.pflux);
-    pool.dxdz = const_cast<double*>(a.pz);
+    unpack_round_args(&a, P, pool);
     // (the object index through readfirstlane: the division runs on the vector unit, and the loads of the row are to be scalar loads)
     const int64_t oi = (int64_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x / (unsigned)segs));
-    const int64_t j0 = round_first + (int64_t)(blockIdx.x % segs) * WG;
-    int64_t j_end = round_first + nrecalc;
-    const int64_t n = P.objects[oi].n_phot;
-    if (j_end > n) j_end = n;
-    if (j0 >= j_end) return;
+    int64_t j0, j_end;
+    if (!round_window(P, oi, (int64_t)(blockIdx.x % segs), WG, round_first, nrecalc, j0, j_end)) return;
     accumulate_segment<NV, WG>(P, pool, pool_start, oi, j0, j_end);
 }
 
@@ -733,18 +755,11 @@ __global__ __launch_bounds__(256, 4) void k_accumulate_round_c2(const RoundArgs 
                                                                 int64_t round_first, int32_t nrecalc, int32_t segs2)
 {
     ims_render_params_t P;
-    P.objects = a.objects; P.sensor = a.sensor; P.image = a.image; P.realized_flux = a.realized_flux;
-    P.nx = a.nx; P.ny = a.ny; P.xmin = a.xmin; P.ymin = a.ymin;
-    P.bf_tag = a.bf_tag; P.bf_slot_shift = a.bf_slot_shift; P.track_static_delta = a.track_static_delta;
     ims_photons_t pool;
-    pool.x = const_cast<double*>(a.px); pool.y = const_cast<double*>(a.py); pool.flux = const_cast<double*>(a.pflux);
-    pool.dxdz = const_cast<double*>(a.pz);
+    unpack_round_args(&a, P, pool);
     const int64_t oi = blockIdx.x / segs2;
-    const int64_t j0 = round_first + (int64_t)(blockIdx.x % segs2) * 512;
-    int64_t j_end = round_first + nrecalc;
-    const int64_t n = P.objects[oi].n_phot;
-    if (j_end > n) j_end = n;
-    if (j0 >= j_end) return;
+    int64_t j0, j_end;
+    if (!round_window(P, oi, (int64_t)(blockIdx.x % segs2), 512, round_first, nrecalc, j0, j_end)) return;
     accumulate_segment2<NV>(P, pool, pool_start, oi, j0, j_end);
 }
 
@@ -755,8 +770,6 @@ __global__ __launch_bounds__(256, 4) void k_accumulate_round_c2(const RoundArgs 
 // one after the other), while one launch that holds the round of MANY objects costs little more than the round of one (C3: 41
 // objects 2.8 x one star).  So the launch takes the argument blocks of up to IMS_JOINT_MAX chains by value and a workgroup
 // finds its chain from the ascending workgroup ends (scalar compares on kernel arguments); the body is the one above.
-constexpr int IMS_JOINT_MAX = 64;
-
 struct JointEnds { int32_t v[IMS_JOINT_MAX]; };      // ascending workgroup ends of the chains of one launch (a chain that sits out: zero width)
 
 struct JointAcc {                           // per chain, constant over the rounds: lives in device memory (ims_plans_run_joint)
@@ -813,19 +826,13 @@ __global__ __launch_bounds__(WG, (NV == 8) ? 2 : 4) void k_accumulate_round_j(co
     typedef const JointAcc __attribute__((address_space(4))) * ConstAcc;
     ConstAcc Jc = (ConstAcc)(uintptr_t)J;
     ims_render_params_t P;
-    P.objects = Jc->a[c].objects; P.sensor = Jc->a[c].sensor; P.image = Jc->a[c].image; P.realized_flux = Jc->a[c].realized_flux;
-    P.nx = Jc->a[c].nx; P.ny = Jc->a[c].ny; P.xmin = Jc->a[c].xmin; P.ymin = Jc->a[c].ymin;
-    P.bf_tag = tag; P.bf_slot_shift = 0; P.track_static_delta = Jc->a[c].track_static_delta;
     ims_photons_t pool;
-    pool.x = const_cast<double*>(Jc->a[c].px); pool.y = const_cast<double*>(Jc->a[c].py); pool.flux = const_cast<double*>(Jc->a[c].pflux);
-    pool.dxdz = const_cast<double*>(Jc->a[c].pz);
+    unpack_round_args(&Jc->a[c], P, pool);
+    P.bf_tag = tag; P.bf_slot_shift = 0;
     const int64_t* pool_start = Jc->pool_start[c];
     const int64_t oi = b / segs;
-    const int64_t j0 = round_first + (int64_t)(b % segs) * WG;
-    int64_t j_end = round_first + nrecalc;
-    const int64_t n = P.objects[oi].n_phot;
-    if (j_end > n) j_end = n;
-    if (j0 >= j_end) return;
+    int64_t j0, j_end;
+    if (!round_window(P, oi, (int64_t)(b % segs), WG, round_first, nrecalc, j0, j_end)) return;
     TileLister tl;
     tl.list = list; tl.count = list_count; tl.round_word = round_word; tl.chain = c; tl.J = J; tl.R = R;
     accumulate_segment<NV, WG>(P, pool, pool_start, oi, j0, j_end, &tl);
@@ -1005,6 +1012,7 @@ __global__ __launch_bounds__(256) void k_init_boundaries(const ims_sensor_t* __r
 // their neighbour's points themselves -- ~12 evaluations of the tree-ring closed form per cell instead of 30 (each is a
 // sqrt, two divisions and a spline).  Same function of (cell, point), so the same bits as k_init_boundaries.
 constexpr int UT = 16;            // tile edge of the boundary kernels (mark_tile_charge assumes 16)
+__host__ __device__ __forceinline__ int tiles_across(int n) { return (n + 1 + UT - 1) / UT; }   // tiles across the n + 1 owner cells of a slot's row / column
 constexpr int IT_NV = 4, IT_NPO = 2 * IT_NV + 2, IT_NVT = 4 * IT_NV + 4;
 
 // tile_prefix (device, prefix sum of the tiles of the slots first_slot ..): a 1-D grid over exactly the tiles of the
@@ -1028,7 +1036,7 @@ __global__ __launch_bounds__(256) void k_init_tiles(const ims_sensor_t* __restri
     }
     const ims_bf_slot_t bs = s.bf_slots[slot];
     const SlotView sl = { bs.xmin, bs.ymin, bs.nx, bs.ny, bs.offset };
-    const int tiles_x = (sl.nx + 1 + UT - 1) / UT, tiles_y = (sl.ny + 1 + UT - 1) / UT;
+    const int tiles_x = tiles_across(sl.nx), tiles_y = tiles_across(sl.ny);
     if (t >= tiles_x * tiles_y) return;
     const TreeRing T = treering_of(s);
     const int lx = threadIdx.x % UT, ly = threadIdx.x / UT;
@@ -1340,7 +1348,7 @@ constexpr int UH = UT + 2 * UQMAX + 1;
 __device__ __forceinline__ bool tile_out_of_reach(const ims_sensor_t& s, const SlotView& sl, int tx, int ty, unsigned int tag)
 {
     if (tag == 0u || s.bf_tile_charge == nullptr) return false;
-    const int tiles_x = (sl.nx + 1 + UT - 1) / UT, tiles_y = (sl.ny + 1 + UT - 1) / UT;
+    const int tiles_x = tiles_across(sl.nx), tiles_y = tiles_across(sl.ny);
     // (the nine marks read together -- a neighbour that does not exist reads the tile's own mark -- not one after the other behind
     // `any ||`: up to nine dependent round trips at the head of a tile that turns out to be out of reach)
     const unsigned char* __restrict__ marks = s.bf_tile_charge;
@@ -1368,7 +1376,7 @@ __global__ __launch_bounds__(256) void k_update_distortions(const ims_sensor_t* 
     const int lo = find_slot(tile_prefix, n_slots, b);
     const ims_bf_slot_t bs = s.bf_slots[first_slot + lo];
     const SlotView sl = { bs.xmin, bs.ymin, bs.nx, bs.ny, bs.offset };
-    const int tiles_x = (sl.nx + 1 + UT - 1) / UT;
+    const int tiles_x = tiles_across(sl.nx);
     const int t = (int)(b - tile_prefix[lo]);
     const int tx0 = (t % tiles_x) * UT, ty0 = (t / tiles_x) * UT;
     if (tile_out_of_reach(s, sl, tx0 / UT, ty0 / UT, tag)) return;
@@ -1700,7 +1708,7 @@ __global__ __launch_bounds__(256) void k_update_distortions_q3(const ims_sensor_
     const int lo = find_slot(tile_prefix, n_slots, b);
     const ims_bf_slot_t bs = s.bf_slots[first_slot + lo];
     const SlotView sl = { bs.xmin, bs.ymin, bs.nx, bs.ny, bs.offset };
-    const int tiles_x = (sl.nx + 1 + UT - 1) / UT;
+    const int tiles_x = tiles_across(sl.nx);
     const int t = (int)(b - tile_prefix[lo]);
     const int tx0 = (t % tiles_x) * UT, ty0 = (t / tiles_x) * UT;
     if (tile_out_of_reach(s, sl, tx0 / UT, ty0 / UT, tag)) return;
@@ -1765,7 +1773,7 @@ __device__ __forceinline__ void update_block_q3(const ims_sensor_t* __restrict__
     const int lo = find_slot(tile_prefix, n_slots, b);
     const ims_bf_slot_t bs = s.bf_slots[first_slot + lo];
     const SlotView sl = { bs.xmin, bs.ymin, bs.nx, bs.ny, bs.offset };
-    const int tiles_x = (sl.nx + 1 + UT - 1) / UT;
+    const int tiles_x = tiles_across(sl.nx);
     const int t = (int)(b - tile_prefix[lo]);
     const int tx0 = (t % tiles_x) * UT, ty0 = (t / tiles_x) * UT;
     if (tile_out_of_reach(s, sl, tx0 / UT, ty0 / UT, tag)) return;
@@ -1873,6 +1881,22 @@ __device__ __forceinline__ void refresh_tile(const ims_sensor_t& s, const SlotVi
     bb[4] = oxmin; bb[5] = oxmax; bb[6] = oymin; bb[7] = oymax;
 }
 
+// which marks carry this round's tag: the tile's own, its right / upper neighbour's `changed` mark, its charge mark; false: none (nothing to refresh)
+struct TileAt { SlotView sl; int tx, ty, tiles_x; };   // (the tagged kernels name one in a block: as plain arguments k_refresh_changed_j takes 32 SGPRs for 30)
+__device__ __forceinline__ bool refresh_flags(const ims_sensor_t& s, const TileAt& T, unsigned int tag, bool& own, bool& right, bool& up, bool& charged)
+{
+    const SlotView& sl = T.sl; const int tx = T.tx, ty = T.ty, tiles_x = T.tiles_x;
+    const unsigned char tg = (unsigned char)tag;
+    // (the four bytes in ONE round trip: the right / upper tile's at the tile's own address where there is none)
+    const bool has_r = tx + 1 < tiles_x, has_u = ty + 1 < tiles_across(sl.ny);
+    const unsigned char t_own = s.bf_tile_changed[cell_index(sl, tx * UT, ty * UT)],
+                        t_right = s.bf_tile_changed[cell_index(sl, (has_r ? tx + 1 : tx) * UT, ty * UT)],
+                        t_up = s.bf_tile_changed[cell_index(sl, tx * UT, (has_u ? ty + 1 : ty) * UT)],
+                        t_charge = s.bf_tile_charge[cell_index(sl, tx * UT, ty * UT)];
+    own = t_own == tg; right = has_r && t_right == tg; up = has_u && t_up == tg; charged = t_charge == tg;
+    return own || right || up || charged;
+}
+
 template <int NV>
 __global__ __launch_bounds__(256) void k_refresh_changed(const ims_sensor_t* __restrict__ sp, int first_slot, int n_slots,
                                                          const int64_t* __restrict__ tile_prefix,
@@ -1885,21 +1909,13 @@ __global__ __launch_bounds__(256) void k_refresh_changed(const ims_sensor_t* __r
     const int lo = find_slot(tile_prefix, n_slots, b);
     const ims_bf_slot_t bs = s.bf_slots[first_slot + lo];
     const SlotView sl = { bs.xmin, bs.ymin, bs.nx, bs.ny, bs.offset };
-    const int tiles_x = (sl.nx + 1 + UT - 1) / UT, tiles_y = (sl.ny + 1 + UT - 1) / UT;
+    const int tiles_x = tiles_across(sl.nx);
     const int t = (int)(b - tile_prefix[lo]);
     const int tx = t % tiles_x, ty = t / tiles_x;
     const bool flags = (tag != 0u) && s.bf_tile_charge != nullptr && s.bf_tile_changed != nullptr;
     bool own = true, right = true, up = true, charged = true;
     if (flags) {
-        const unsigned char tg = (unsigned char)tag;
-        // (the four bytes in ONE round trip: the right / upper tile's at the tile's own address where there is none)
-        const bool has_r = tx + 1 < tiles_x, has_u = ty + 1 < tiles_y;
-        const unsigned char t_own = s.bf_tile_changed[cell_index(sl, tx * UT, ty * UT)],
-                            t_right = s.bf_tile_changed[cell_index(sl, (has_r ? tx + 1 : tx) * UT, ty * UT)],
-                            t_up = s.bf_tile_changed[cell_index(sl, tx * UT, (has_u ? ty + 1 : ty) * UT)],
-                            t_charge = s.bf_tile_charge[cell_index(sl, tx * UT, ty * UT)];
-        own = t_own == tg; right = has_r && t_right == tg; up = has_u && t_up == tg; charged = t_charge == tg;
-        if (!(own || right || up || charged)) return;
+        const TileAt T = { sl, tx, ty, tiles_x }; if (!refresh_flags(s, T, tag, own, right, up, charged)) return;
     }
     PROBE(17);
     refresh_tile<NV>(s, sl, tx, ty, own, right, up, charged, changed, fold_image);
@@ -1919,21 +1935,13 @@ __global__ __launch_bounds__(256) void k_refresh_changed_j(const JointUpd* __res
     const int lo = find_slot(tile_prefix, joint_entry(&R->ns, c), b);
     const ims_bf_slot_t bs = s.bf_slots[U->first_slot[c] + lo];
     const SlotView sl = { bs.xmin, bs.ymin, bs.nx, bs.ny, bs.offset };
-    const int tiles_x = (sl.nx + 1 + UT - 1) / UT, tiles_y = (sl.ny + 1 + UT - 1) / UT;
+    const int tiles_x = tiles_across(sl.nx);
     const int t = (int)(b - tile_prefix[lo]);
     const int tx = t % tiles_x, ty = t / tiles_x;
     const bool flags = (tag != 0u) && s.bf_tile_charge != nullptr && s.bf_tile_changed != nullptr;
     bool own = true, right = true, up = true, charged = true;
     if (flags) {
-        const unsigned char tg = (unsigned char)tag;
-        // (the four bytes in ONE round trip: the right / upper tile's at the tile's own address where there is none)
-        const bool has_r = tx + 1 < tiles_x, has_u = ty + 1 < tiles_y;
-        const unsigned char t_own = s.bf_tile_changed[cell_index(sl, tx * UT, ty * UT)],
-                            t_right = s.bf_tile_changed[cell_index(sl, (has_r ? tx + 1 : tx) * UT, ty * UT)],
-                            t_up = s.bf_tile_changed[cell_index(sl, tx * UT, (has_u ? ty + 1 : ty) * UT)],
-                            t_charge = s.bf_tile_charge[cell_index(sl, tx * UT, ty * UT)];
-        own = t_own == tg; right = has_r && t_right == tg; up = has_u && t_up == tg; charged = t_charge == tg;
-        if (!(own || right || up || charged)) return;
+        const TileAt T = { sl, tx, ty, tiles_x }; if (!refresh_flags(s, T, tag, own, right, up, charged)) return;
     }
     refresh_tile<NV>(s, sl, tx, ty, own, right, up, charged, changed);
 }
@@ -1947,7 +1955,7 @@ __global__ __launch_bounds__(256) void k_refresh_changed_j(const JointUpd* __res
 // change (the tile itself, its right or its upper neighbour within reach) to a second one; the update and refresh launches
 // then hold a fraction of the workgroups and walk the lists.  Same decisions as the tagged kernels, tile by tile: same bits.
 struct JointLists {
-    unsigned long long* upd;            // entries: chain << 58 | slot of the class << 32 | tile of the slot
+    unsigned long long* upd;            // entries: pack_tile_entry
     unsigned long long* ref;
     int* count;                         // [parity][2]: entries of upd / ref
 };
@@ -1987,7 +1995,7 @@ __global__ __launch_bounds__(256) void k_build_active_j(const JointUpd* __restri
     if (g < n_tiles) {
         const ims_bf_slot_t bs = s.bf_slots[U->first_slot[c] + my_lo];
         const SlotView sl = { bs.xmin, bs.ymin, bs.nx, bs.ny, bs.offset };
-        const int tiles_x = (sl.nx + 1 + UT - 1) / UT, tiles_y = (sl.ny + 1 + UT - 1) / UT;
+        const int tiles_x = tiles_across(sl.nx), tiles_y = tiles_across(sl.ny);
         const int tx = my_t % tiles_x, ty = my_t / tiles_x;
         const unsigned char tg = (unsigned char)tag;
         // charge marks of the 4 x 4 window (-1 .. 2)^2 around the tile, as bits
@@ -2032,7 +2040,7 @@ __global__ __launch_bounds__(256) void k_build_active_j(const JointUpd* __restri
             in_reach = any; bounds = any;
         }
     }
-    const unsigned long long entry = ((unsigned long long)c << 58) | ((unsigned long long)(unsigned int)my_lo << 32) | (unsigned int)my_t;
+    const unsigned long long entry = pack_tile_entry(c, my_lo, my_t);
     {
         const unsigned long long mask = __builtin_amdgcn_ballot_w64(in_reach);
         if (mask != 0ull) {
@@ -2057,11 +2065,11 @@ __global__ __launch_bounds__(256) void k_build_active_j(const JointUpd* __restri
 template <int NV>
 __device__ __forceinline__ void update_listed_tile(const JointUpd* __restrict__ U, unsigned long long e, unsigned int tag, UpdateLds<NV>& L)
 {
-    const int c = (int)(e >> 58), lo = (int)((e >> 32) & 0x3FFFFFFu), t = (int)(e & 0xFFFFFFFFu);
+    int c, lo, t; unpack_tile_entry(e, c, lo, t);
     const ims_sensor_t& s = *U->sp[c];
     const ims_bf_slot_t bs = s.bf_slots[U->first_slot[c] + lo];
     const SlotView sl = { bs.xmin, bs.ymin, bs.nx, bs.ny, bs.offset };
-    const int tiles_x = (sl.nx + 1 + UT - 1) / UT;
+    const int tiles_x = tiles_across(sl.nx);
     const int tx0 = (t % tiles_x) * UT, ty0 = (t / tiles_x) * UT;
     const double* dl_global = U->dl[c];
 #ifdef IMS_HIST
@@ -2112,22 +2120,14 @@ __global__ __launch_bounds__(256) void k_refresh_list_j(const JointUpd* __restri
     const int n = Ls.count[2 * parity + (from_upd ? 0 : 1)];
     const unsigned long long* __restrict__ list = from_upd ? Ls.upd : Ls.ref;
     for (int i = (int)blockIdx.x; i < n; i += (int)gridDim.x) {
-        const unsigned long long e = list[i];
-        const int c = (int)(e >> 58), lo = (int)((e >> 32) & 0x3FFFFFFu), t = (int)(e & 0xFFFFFFFFu);
+        int c, lo, t; unpack_tile_entry(list[i], c, lo, t);
         const ims_sensor_t& s = *U->sp[c];
         const ims_bf_slot_t bs = s.bf_slots[U->first_slot[c] + lo];
         const SlotView sl = { bs.xmin, bs.ymin, bs.nx, bs.ny, bs.offset };
-        const int tiles_x = (sl.nx + 1 + UT - 1) / UT, tiles_y = (sl.ny + 1 + UT - 1) / UT;
+        const int tiles_x = tiles_across(sl.nx);
         const int tx = t % tiles_x, ty = t / tiles_x;
-        const unsigned char tg = (unsigned char)tag;
-        // (the four bytes in ONE round trip: the right / upper tile's at the tile's own address where there is none)
-        const bool has_r = tx + 1 < tiles_x, has_u = ty + 1 < tiles_y;
-        const unsigned char t_own = s.bf_tile_changed[cell_index(sl, tx * UT, ty * UT)],
-                            t_right = s.bf_tile_changed[cell_index(sl, (has_r ? tx + 1 : tx) * UT, ty * UT)],
-                            t_up = s.bf_tile_changed[cell_index(sl, tx * UT, (has_u ? ty + 1 : ty) * UT)],
-                            t_charge = s.bf_tile_charge[cell_index(sl, tx * UT, ty * UT)];
-        const bool own = t_own == tg, right = has_r && t_right == tg, up = has_u && t_up == tg, charged = t_charge == tg;
-        if (!(own || right || up || charged)) continue;
+        bool own, right, up, charged;
+        if (!refresh_flags(s, { sl, tx, ty, tiles_x }, tag, own, right, up, charged)) continue;
         refresh_tile<NV>(s, sl, tx, ty, own, right, up, charged, (const unsigned char*)U->changed[c]);
     }
 }
@@ -3655,6 +3655,12 @@ int ims_accumulate_round(const ims_render_params_t* params, const ims_photons_t*
     return IMS_OK;
 }
 
+static RoundArgs round_args(const ims_render_params_t& P, const ims_photons_t& pool)
+{
+    return { P.objects, P.sensor, P.image, P.realized_flux, pool.x, pool.y, pool.flux, pool.dxdz, P.nx, P.ny, P.xmin, P.ymin,
+             P.bf_tag, P.bf_slot_shift, P.track_static_delta, 0 };
+}
+
 // ims_accumulate_round launched with the compact argument block (4 vertices per edge, 256-thread workgroups)
 static int accumulate_round_compact(const ims_render_params_t* params, const ims_photons_t* pool, const int64_t* pool_start, int32_t round,
                                     int32_t nrecalc, int32_t n_active, int32_t num_vertices, void* stream)
@@ -3665,11 +3671,7 @@ static int accumulate_round_compact(const ims_render_params_t* params, const ims
     if (!params || !params->objects || !params->image || !pool || !pool_start || !pool->converted) return set_err(IMS_ERR_ARG, "NULL argument");
     const int32_t segs = (nrecalc + 255) / 256;
     if ((int64_t)n_active * segs > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "too many workgroups for one round");
-    RoundArgs a;
-    a.objects = params->objects; a.sensor = params->sensor; a.image = params->image; a.realized_flux = params->realized_flux;
-    a.px = pool->x; a.py = pool->y; a.pflux = pool->flux; a.pz = pool->dxdz;
-    a.nx = params->nx; a.ny = params->ny; a.xmin = params->xmin; a.ymin = params->ymin;
-    a.bf_tag = params->bf_tag; a.bf_slot_shift = params->bf_slot_shift; a.track_static_delta = params->track_static_delta; a.pad = 0;
+    const RoundArgs a = round_args(*params, *pool);
     LaunchTimer tm((hipStream_t)stream, 4);
     if (g_tune.round_two_segments) {
         const int32_t segs2 = (nrecalc + 511) / 512;
@@ -3759,7 +3761,7 @@ int ims_sensor_init_boundaries(const ims_sensor_t* sensor_dev, const ims_sensor_
         while (a < end) {
             auto tiles_of = [&](int k) {
                 const ims_bf_slot_t& b = sensor_host->bf_slots[k];
-                return (int64_t)((b.nx + 1 + UT - 1) / UT) * ((b.ny + 1 + UT - 1) / UT);
+                return (int64_t)tiles_across(b.nx) * tiles_across(b.ny);
             };
             int64_t hi = tiles_of(a), sum = hi;
             int z = a + 1;
@@ -3905,6 +3907,13 @@ static int32_t count_above(const int64_t* n_phot, int32_t n, int64_t threshold)
         if (n_phot[mid] > threshold) lo = mid + 1; else hi = mid;
     }
     return lo;
+}
+
+// tiles of the chain's regions that go on after round `round` (the objects with photons beyond it)
+static int64_t tiles_going_on(const ims_chain_t& ch, int32_t round, int32_t nrecalc)
+{
+    const int32_t n_cont = count_above(ch.n_phot, ch.n_objects, (int64_t)(round + 1) * nrecalc);
+    return n_cont > 0 ? ch.tile_prefix_host[n_cont] : 0;
 }
 
 // IMS_PLAN_ROUNDS: the rounds of several chain classes, enqueued round by round so that every chain advances at the same pace
@@ -4321,10 +4330,7 @@ int ims_plans_run_joint(void* const* plans, int32_t n_plans, void* joint_stream,
     const long long list_min_tiles = g_tune.joint_list_min;
     const double list_fraction = g_tune.active_fraction;
     int64_t tiles_max = 0;                                   // round 0 has them all
-    for (const Act& a : act) {
-        const int32_t n_cont = count_above(a.ch->n_phot, a.ch->n_objects, (int64_t)nrecalc);
-        tiles_max += n_cont > 0 ? a.ch->tile_prefix_host[n_cont] : 0;
-    }
+    for (const Act& a : act) tiles_max += tiles_going_on(*a.ch, 0, nrecalc);
     const bool lists = lists_on && tiles_max > list_min_tiles;
     struct Ring { JointTables* dev; hipEvent_t free_after; bool used; bool busy; unsigned long long* upd; unsigned long long* ref; int* count; int64_t cap;
                   JointRound* rounds_dev; JointRound* rounds_pin; int64_t rounds_cap; unsigned int* words; };
@@ -4388,10 +4394,7 @@ int ims_plans_run_joint(void* const* plans, int32_t n_plans, void* joint_stream,
     if (search_lists) HIP_TRY(hipMemsetAsync(words_dev, 0, (size_t)tiles_max * sizeof(unsigned int), js));
     // a chain's tile words: behind those of the chains before it (round 0 lists from all the regions that go on)
     std::vector<int64_t> word_off(act.size() + 1, 0);
-    for (size_t k = 0; k < act.size(); ++k) {
-        const int32_t n_cont = count_above(act[k].ch->n_phot, act[k].ch->n_objects, (int64_t)nrecalc);
-        word_off[k + 1] = word_off[k] + (n_cont > 0 ? act[k].ch->tile_prefix_host[n_cont] : 0);
-    }
+    for (size_t k = 0; k < act.size(); ++k) word_off[k + 1] = word_off[k] + tiles_going_on(*act[k].ch, 0, nrecalc);
     bool dpp_ok = true;
     for (size_t k0 = 0; k0 < act.size(); k0 += JOINT_CHUNK) {
         JointChunk Ck;
@@ -4399,12 +4402,8 @@ int ims_plans_run_joint(void* const* plans, int32_t n_plans, void* joint_stream,
         for (size_t k = 0; k < (size_t)JOINT_CHUNK; ++k) {
             const Act& a = act[k0 + k < act.size() ? k0 + k : 0];         // entries beyond the last repeat chain 0 (never selected: zero width)
             const ims_chain_t& ch = *a.ch;
-            const ims_render_params_t& P = *ch.params;
-            RoundArgs& ra = Ck.a[k];
-            ra.objects = P.objects; ra.sensor = P.sensor; ra.image = P.image; ra.realized_flux = P.realized_flux;
-            ra.px = ch.pool->x; ra.py = ch.pool->y; ra.pflux = ch.pool->flux; ra.pz = ch.pool->dxdz;
-            ra.nx = P.nx; ra.ny = P.ny; ra.xmin = P.xmin; ra.ymin = P.ymin;
-            ra.bf_tag = 0; ra.bf_slot_shift = 0; ra.track_static_delta = P.track_static_delta; ra.pad = 0;
+            Ck.a[k] = round_args(*ch.params, *ch.pool);
+            Ck.a[k].bf_tag = 0; Ck.a[k].bf_slot_shift = 0;                    // (the launch brings the round's tag)
             Ck.pool_start[k] = ch.pool_start;
             Ck.sp[k] = a.pl->d_sensor_dev; Ck.tile_prefix[k] = ch.tile_prefix; Ck.changed[k] = a.pl->d_changed;
             Ck.dl[k] = a.pl->d_sensor_host->bf_dl; Ck.first_slot[k] = ch.first_slot;
@@ -4428,7 +4427,7 @@ int ims_plans_run_joint(void* const* plans, int32_t n_plans, void* joint_stream,
                 const ims_chain_t& ch = *act[k].ch;
                 n_act = count_above(ch.n_phot, ch.n_objects, (int64_t)r * nrecalc);
                 n_cont = count_above(ch.n_phot, ch.n_objects, (int64_t)(r + 1) * nrecalc);
-                tk = n_cont > 0 ? ch.tile_prefix_host[n_cont] : 0;
+                tk = tiles_going_on(ch, r, nrecalc);
             }
             tiles += tk;
             build_wgs += (tk + 255) / 256;

@@ -288,6 +288,43 @@ def test_two_segment_round_search_gives_the_one_segment_result(torch_cuda, monke
     assert_bits_equal(out[0][0], orc.image, "image vs oracle")
 
 
+def test_round_kernels_off_the_default_path_give_the_default_result(torch_cuda, monkeypatch):
+    """The forms of a round that the defaults never launch end with the image, realized fluxes and sensor state of the
+    default ones -- and with the oracle's image: ims_tuning_t.round_compact = 0 (k_accumulate_round with the 1.4-KB launch
+    parameters, the form behind ims_accumulate_round) against the compact argument block, each with the DPP form of the update
+    for every launch (upd_dpp_max out of reach) and with the SGPR form for every launch (upd_dpp = 0).  Rounds of 300 photons:
+    two workgroups per object, the second ragged.  179 objects is the smallest catalog of this scene with more than 64 regions
+    that go on past round 0, so find_slot takes its two-level path; their stamps are not whole tiles."""
+    from imsim_amd.engine import Renderer
+    from oracle import orc_loader
+    nrecalc = 300
+    scene, objects = _c3_case(n_obj=179)
+    goes_on = objects["n_phot"] > nrecalc
+    assert goes_on.sum() > 64
+    stamp_nx = objects["stamp_xmax"][goes_on] - objects["stamp_xmin"][goes_on] + 1
+    assert ((stamp_nx + 1) % 16 != 0).any()
+    out = []
+    for compact in ("1", "0"):
+        for dpp, dpp_max in (("1", "1000000000"), ("0", "128")):
+            monkeypatch.setenv("IMS_ROUND_COMPACT", compact)
+            monkeypatch.setenv("IMS_UPD_DPP", dpp)
+            monkeypatch.setenv("IMS_UPD_DPP_MAX", dpp_max)
+            r = Renderer(scene)
+            real = torch_cuda.zeros(len(objects), dtype=torch_cuda.float64, device="cuda")
+            r.render_lsst_image(objects, nrecalc=nrecalc, realized=real)
+            r.synchronize()
+            out.append((r.image_numpy(), real.cpu().numpy(), _sensor_arrays_gpu(r)))
+    assert out[0][0].sum() > 0
+    for o in out[1:]:
+        assert_bits_equal(o[0], out[0][0], "image")
+        assert_bits_equal(o[1], out[0][1], "realized flux")
+        for name in ("boundary", "bounds", "delta"):
+            assert_bits_equal(o[2][name], out[0][2][name], f"sensor {name}")
+    orc = orc_loader.OracleScene(scene)
+    orc.render_lsst_image(objects, nrecalc=nrecalc)
+    assert_bits_equal(out[0][0], orc.image, "image vs oracle")
+
+
 def test_lazy_static_renderer_makes_the_state_when_something_needs_it(torch_cuda):
     """lazy_static used to sit in the renderer's base parameters, so pooled accumulates and the sky's pixel areas ran on a
     slot 0 that was never initialised.  Now the flag travels with the fused render only; an entry point that reads the stored
