@@ -682,7 +682,8 @@ def _c5_objects(cat, phot, scene):
     from . import lsst_image
     v = c5_visit_fft()
     is_fft = lsst_image.LSST_ImageBuilderBase._use_fft(cat, cat["nominal_flux"], v["fwhm_total"], C5_FFT_SB_THRESH, v["kpsf"], ())
-    t.fft_mask = (is_fft & (np.asarray(cat["kind"]) < 3))[phot > 0]
+    from . import fft_draw
+    t.fft_mask = is_fft[phot > 0] & fft_draw.has_kspace_form(np.asarray(cat["kind"])[phot > 0], objects)     # LSST_ImageBuilder.prepare's rule
     return t, sizes
 
 

@@ -18,6 +18,42 @@ IMS_DEV double ktable_lookup(const ims_lin_tables_t& t, int table, double arg)
     return v[i] + a * (v[i + 1] - v[i]);
 }
 
+// sinc(k pixel_scale / 2), 1 at 0: the pixel response along one axis
+IMS_DEV double pixel_response(double k, double pixel_scale)
+{
+    const double h = 0.5 * k * pixel_scale;
+    if (h == 0.0) return 1.0;
+    double s, c;
+    dsincos(h, s, c);
+    return s / h;
+}
+
+// unit-flux box (IMS_PROF_BOX): the host folds length and width into jac, so the profile is the unit square's transform at q = J^T k,
+// sinc(qx / 2) sinc(qy / 2).  sinc is even and taken of |h|: a box turned by 90 degrees has components of q of 1e-16 of either sign
+// (cos(pi / 2) is not 0), and dsincos reduces a small NEGATIVE argument to a fraction of a turn just below 1 -- good to 1e-16
+// absolutely, which is all a phase needs, but sin(h) / h wants it relative to h.
+IMS_DEV double sinc_even(double h)
+{
+    h = fabs(h);
+    if (h == 0.0) return 1.0;
+    double s, c;
+    dsincos(h, s, c);
+    return s / h;
+}
+IMS_DEV double box_response(double qx, double qy)
+{
+    return sinc_even(0.5 * qx) * sinc_even(0.5 * qy);
+}
+// sinc(h) from a sine the caller formed by angle addition (the fill kernel's LDS tables).  Such a sine is good ABSOLUTELY -- to a few
+// 1e-16 from the arithmetic, plus some ulps of the LARGEST PART of the sum, since the parts are rounded one by one (k_fft_kspace_fill
+// has the figures and keeps the tables to grids where that stays small) -- so the quotient loses relative accuracy as h -> 0: below
+// BOX_SMALL_H the point takes the plain form.
+constexpr double BOX_SMALL_H = 0.25;
+IMS_DEV double sinc_from_sine(double h, double s)
+{
+    return fabs(h) < BOX_SMALL_H ? sinc_even(h) : s / h;
+}
+
 // spectrum of object o (profile x PSF MTFs x pixel response x centring phase) at the k-vector (kx, ky) [rad/arcsec]
 IMS_DEV void kspace_at(const ims_fft_params_t& P, const ims_fft_object_t& o, double kx, double ky, double& re, double& im)
 {
@@ -27,6 +63,8 @@ IMS_DEV void kspace_at(const ims_fft_params_t& P, const ims_fft_object_t& o, dou
         const double qx = o.jac[0] * kx + o.jac[2] * ky;
         const double qy = o.jac[1] * kx + o.jac[3] * ky;
         amp = amp * ktable_lookup(P.ktables, o.prof_ktable, sqrt(qx * qx + qy * qy) * o.prof_scale);
+    } else if (o.prof_ktable == IMS_PROF_BOX) {
+        amp = amp * box_response(o.jac[0] * kx + o.jac[2] * ky, o.jac[1] * kx + o.jac[3] * ky);
     }
     const double k2 = kx * kx + ky * ky;
     for (int c = 0; c < P.n_kpsf; ++c) {
@@ -54,18 +92,12 @@ IMS_DEV void kspace_at(const ims_fft_params_t& P, const ims_fft_object_t& o, dou
 // kspace_at(kx, ky) and kspace_at(kx, -ky) return.  (The k-space fill was three exponentials, a logarithm and three sine / cosine
 // pairs per point: 27 % of the FFT branch at throughput, all arithmetic; round 6.)
 // tab != nullptr: the three pixel-response factors (s / h, or 1 where h is 0 -- a product with 1 is the value itself) come from the
-// caller's tables {along x; along y for ky; along y for -ky}, formed by pixel_response below: the same function of the same argument.
-IMS_DEV double pixel_response(double k, double pixel_scale)
-{
-    const double h = 0.5 * k * pixel_scale;
-    if (h == 0.0) return 1.0;
-    double s, c;
-    dsincos(h, s, c);
-    return s / h;
-}
-
+// caller's tables {along x; along y for ky; along y for -ky}, formed by pixel_response above: the same function of the same argument.
+// box != nullptr (IMS_PROF_BOX objects only): {sin, cos of the column part of qx / 2; sin, cos of the column part of qy / 2; sin, cos
+// of the row part of qx / 2 for ky; sin, cos of the row part of qy / 2 for ky} -- qx / 2 and qy / 2 are affine in the grid indices,
+// the sines of the sums follow by angle addition (row -ky: the row parts' sines change sign) instead of four dsincos per pair.
 IMS_DEV void kspace_pair(const ims_fft_params_t& P, const ims_fft_object_t& o, double kx, double ky, double& re, double& im,
-                         double& re2, double& im2, const double* tab = nullptr)
+                         double& re2, double& im2, const double* tab = nullptr, const double* box = nullptr)
 {
     const double kym = -ky;
     double amp = o.flux, amp2 = o.flux;
@@ -76,6 +108,18 @@ IMS_DEV void kspace_pair(const ims_fft_params_t& P, const ims_fft_object_t& o, d
         const double qx2 = o.jac[0] * kx + o.jac[2] * kym;
         const double qy2 = o.jac[1] * kx + o.jac[3] * kym;
         amp2 = amp2 * ktable_lookup(P.ktables, o.prof_ktable, sqrt(qx2 * qx2 + qy2 * qy2) * o.prof_scale);
+    } else if (o.prof_ktable == IMS_PROF_BOX) {
+        // not radial: rows i and n - i get a factor each, as the sheared k-table profile does
+        const double qx = o.jac[0] * kx + o.jac[2] * ky, qy = o.jac[1] * kx + o.jac[3] * ky;
+        const double qx2 = o.jac[0] * kx + o.jac[2] * kym, qy2 = o.jac[1] * kx + o.jac[3] * kym;
+        if (box != nullptr) {
+            const double ax = box[0] * box[5], bx = box[1] * box[4], ay = box[2] * box[7], by = box[3] * box[6];
+            amp = amp * (sinc_from_sine(0.5 * qx, ax + bx) * sinc_from_sine(0.5 * qy, ay + by));
+            amp2 = amp2 * (sinc_from_sine(0.5 * qx2, ax - bx) * sinc_from_sine(0.5 * qy2, ay - by));
+        } else {
+            amp = amp * box_response(qx, qy);
+            amp2 = amp2 * box_response(qx2, qy2);
+        }
     }
     const double k2 = kx * kx + ky * ky;
     for (int c = 0; c < P.n_kpsf; ++c) {

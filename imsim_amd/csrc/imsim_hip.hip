@@ -2290,17 +2290,30 @@ __device__ __forceinline__ double rbuf_value(const double* __restrict__ rbuf, in
 // LDS tables of the pixel response for a workgroup whose span lies inside ONE object's half spectrum (every workgroup of a grid of
 // 1 024 or more): sinc along x for every column of the row, sinc along y (for ky and for -ky) for the few rows the span covers.
 constexpr int FILL_NH_MAX = 2049, FILL_ROWS_MAX = 264;      // grids up to 4096 (larger ones: no tables); 20 KB of LDS
+// The same workgroup on a box (IMS_PROF_BOX): qx / 2 = A j + B i' and qy / 2 = C j + D i' are affine in the grid indices, so their sines
+// come from {sin, cos} of (A j, C j) per column and of (B i', D i') per row by angle addition.  The columns are split in two levels,
+// j = 64 jh + jl (64 + 5 entries; one level and the rows would pass the 32 KB a workgroup may hold with five on a CU), the rows are
+// stored for +i' only (the mirrored row changes the sign of the sines).  10.7 KB more: 31.3 KB per workgroup.
+// Grids up to BOX_NFFT_MAX only.  The parts A jl, A 64 jh and B i' are rounded one by one, so where they cancel the sum misses the
+// h the plain form takes by some ulps of the PARTS, and sin / h by that over h: it grows with trail length x grid size (against the
+// numpy restatement of the tests, per unit flux: 2e-16 for 12" on 256, 3e-16 to 2e-15 for 30" on 512, 3e-14 to 6e-14 for 150" on 2048
+// and 8e-14 to 1e-13 for 400" on 4096 in a host emulation of this arithmetic behind Gaussians of sigma 0.4" to 0.3" -- the plain
+// form rounds h as numpy does and stays at 1.4e-15).
+// Neither is nearer to the exact spectrum, but larger grids keep the plain form and the bound the tests hold.
+constexpr int BOX_LO = 64, BOX_NFFT_MAX = 512, BOX_HI_MAX = (BOX_NFFT_MAX / 2 + 1 + BOX_LO - 1) / BOX_LO;
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_fft_kspace_fill(const ims_fft_params_t P, const ims_fft_object_t* __restrict__ objs,
                                                          int64_t n_objects, const int64_t* __restrict__ prefix, int64_t n_elems, int64_t span,
                                                          double* __restrict__ kbuf)
 {
     __shared__ double sinc_x[FILL_NH_MAX];
     __shared__ double sinc_y[2 * FILL_ROWS_MAX];
+    __shared__ double box_col[4 * (BOX_LO + BOX_HI_MAX)];
+    __shared__ double box_row[4 * FILL_ROWS_MAX];
     // (uniform over the workgroup: formed from the block's number and scalar loads)
     const int64_t wg_begin = (int64_t)blockIdx.x * span;
     int64_t wg_end = wg_begin + span;
     if (wg_end > n_elems) wg_end = n_elems;
-    bool tables = false;
+    bool tables = false, box_tables = false;
     int row_first = 0;
     if (P.n_alias <= 0 && wg_begin < wg_end) {
         const int64_t o0 = find_prefix(prefix, n_objects, wg_begin);
@@ -2318,6 +2331,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
                     sinc_y[r] = pixel_response((r & 1) ? -ky : ky, P.pixel_scale);
                 }
                 tables = true;
+                const ims_fft_object_t& ob0 = objs[o0];
+#ifndef IMS_FILL_BOX_PLAIN                 // (-DIMS_FILL_BOX_PLAIN: the box by box_response's dsincos everywhere, to measure against)
+                if (ob0.prof_ktable == IMS_PROF_BOX && n <= BOX_NFFT_MAX) {
+                    const int n_hi = (nh + BOX_LO - 1) / BOX_LO;
+                    for (int t = threadIdx.x; t < BOX_LO + n_hi; t += 256) {
+                        const double kx = (double)(t < BOX_LO ? t : BOX_LO * (t - BOX_LO)) * dk;
+                        dsincos(0.5 * (ob0.jac[0] * kx), box_col[4 * t], box_col[4 * t + 1]);
+                        dsincos(0.5 * (ob0.jac[1] * kx), box_col[4 * t + 2], box_col[4 * t + 3]);
+                    }
+                    for (int r = threadIdx.x; r < row_last - row_first + 1; r += 256) {
+                        const double ky = (double)(row_first + r) * dk;
+                        dsincos(0.5 * (ob0.jac[2] * ky), box_row[4 * r], box_row[4 * r + 1]);
+                        dsincos(0.5 * (ob0.jac[3] * ky), box_row[4 * r + 2], box_row[4 * r + 3]);
+                    }
+                    box_tables = true;
+                }
+#endif
                 __syncthreads();
             }
         }
@@ -2337,7 +2367,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
             if (i > 0 && i < half) {
                 const double dk = TWO_PI / ((double)n * P.pixel_scale);
                 double re2, im2;
-                if (tables) {
+                if (box_tables) {
+                    const double tab[3] = { sinc_x[j], sinc_y[2 * (i - row_first)], sinc_y[2 * (i - row_first) + 1] };
+                    const double* lo = box_col + 4 * (j & (BOX_LO - 1));
+                    const double* hi = box_col + 4 * (BOX_LO + j / BOX_LO);
+                    const double* rw = box_row + 4 * (i - row_first);
+                    const double box[8] = { fma(lo[0], hi[1], lo[1] * hi[0]), fma(lo[1], hi[1], -(lo[0] * hi[0])),
+                                            fma(lo[2], hi[3], lo[3] * hi[2]), fma(lo[3], hi[3], -(lo[2] * hi[2])),
+                                            rw[0], rw[1], rw[2], rw[3] };
+                    kspace_pair(P, o, (double)j * dk, (double)i * dk, re, im, re2, im2, tab, box);
+                } else if (tables) {
                     const double tab[3] = { sinc_x[j], sinc_y[2 * (i - row_first)], sinc_y[2 * (i - row_first) + 1] };
                     kspace_pair(P, o, (double)j * dk, (double)i * dk, re, im, re2, im2, tab);
                 } else {

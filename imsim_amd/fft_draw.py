@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _abi, tables, tuning
 from ._abi import FFT_OBJECT_DTYPE, FftParams, KPsf
+from .catalog import KIND_STREAK
 
 KOLMOGOROV_K0 = 2.992934 * 0.9758634299       # k0 * fwhm for exp(-(k/k0)^(5/3))  [rad/arcsec * arcsec]
 
@@ -102,11 +103,13 @@ def kpsf_peak_per_flux(kpsf, ktables=None, q_step=None, n_base=2):
     return out
 
 
-def max_surface_brightness(flux, kind, hlr, fwhm_total=None, pixel_scale=0.2, sersic_n=None, jac_det=None, psf_peaks=None):
+def max_surface_brightness(flux, kind, hlr, fwhm_total=None, pixel_scale=0.2, sersic_n=None, jac_det=None, psf_peaks=None,
+                           box_area=None):
     """`Convolve(gal_achrom, fft_psf).withFlux(F).max_sb / 2 * pixel_scale^2` [photons/pixel], the quantity
     get_fft_psf_maybe compares with fft_sb_thresh (imsim/psf_utils.py:201-212).  GalSim's max_sb of a convolution is the
     estimate that is exact for Gaussians: F / sum_i (1 / peak_i) with peak_i the central surface brightness per unit
     flux of component i (a DeltaFunction contributes nothing).  Sersic: b^2n / (2 pi n Gamma(2n) hlr^2 |det J|).
+    Streak (galsim.Box): 1 / (length width), Box.max_sb per unit flux, with box_area = length x width [arcsec^2] per object.
     psf_peaks: kpsf_peak_per_flux of the FFT-mode PSF; without it a single Gaussian of FWHM fwhm_total stands in."""
     from scipy import special
     flux = np.asarray(flux, dtype=np.float64)
@@ -128,9 +131,34 @@ def max_surface_brightness(flux, kind, hlr, fwhm_total=None, pixel_scale=0.2, se
         if jac_det is not None:
             peak = peak / np.abs(np.asarray(jac_det, dtype=np.float64)[gal])
         inv[gal] = inv[gal] + 1.0 / peak
-    other = (~gal) & (kind != 0)        # knots, streaks, images: never FFT-drawn here; a broad stand-in keeps them photon-shot
+    box = (kind == KIND_STREAK) if box_area is not None else np.zeros(kind.shape, dtype=bool)
+    if box.any():
+        inv[box] = inv[box] + np.broadcast_to(np.asarray(box_area, dtype=np.float64), kind.shape)[box]
+    other = (~gal) & (~box) & (kind != 0)   # knots and FITS images have no k-space form here: a broad stand-in keeps them photon-shot
     inv[other] = np.inf
     return flux / inv / 2.0 * pixel_scale ** 2
+
+
+def has_kspace_form(kind, objects=None, pixel_scale=0.2):
+    """Which objects the FFT branch can draw at all: points, Sersic profiles and streaks (galsim.Box).  RandomKnots and FITS-image
+    objects have no k-space form here and stay photon-shot whatever their flux.  So does a streak that does not fit the periodic
+    grid its stamp gives it (objects: the OBJECT_DTYPE rows, same length as kind) -- a good stamp size capped at catalog.NMAX, or a
+    stamp size given by the user, can be shorter than the trail, which would then wrap round the grid, where GalSim raises
+    GalSimFFTSizeError.  Deliberate: the trail is still drawn, by photons.  The test is on the box's extent along the pixel axes,
+    |J| (length, width) with J = s winv R(pa), against nfft * pixel_scale."""
+    kind = np.asarray(kind)
+    box = kind == KIND_STREAK
+    ok = (kind < 3) | box
+    if objects is not None and box.any():
+        o = objects[box]
+        size = o["stamp_xmax"] - o["stamp_xmin"] + 1                    # the grid build_fft_objects will take
+        grid = np.array([next_fft_size(int(n)) for n in size], dtype=np.float64) * pixel_scale
+        w, j = o["winv"] * pixel_scale, o["jac"]
+        L, W = o["prof_scale"], o["prof_aux"]
+        ex = np.abs(w[:, 0] * j[:, 0] + w[:, 1] * j[:, 2]) * L + np.abs(w[:, 0] * j[:, 1] + w[:, 1] * j[:, 3]) * W
+        ey = np.abs(w[:, 2] * j[:, 0] + w[:, 3] * j[:, 2]) * L + np.abs(w[:, 2] * j[:, 1] + w[:, 3] * j[:, 3]) * W
+        ok[box] = np.maximum(ex, ey) <= grid
+    return ok
 
 
 def use_fft(nominal_flux, kind, hlr, fwhm_total, fft_sb_thresh, **kw):
@@ -145,9 +173,9 @@ def use_fft(nominal_flux, kind, hlr, fwhm_total, fft_sb_thresh, **kw):
 def profile_ktable_ids(scene, prof_table, n_extra_ktables=0, n_base=2):
     """k-table id of every object from its radial table id: tables 0 / 1 (n = 1 / 4) keep their ids, the scene's
     further Sersic indices sit behind the n_extra_ktables PSF tables in the order of scene.sersic_extra_n;
-    everything else (points) is -1."""
+    a streak's box keeps IMS_PROF_BOX (-2, the closed form of kspace_at); everything else (points) is -1."""
     prof_table = np.asarray(prof_table)
-    out = np.where((prof_table == 0) | (prof_table == 1), prof_table, -1).astype(np.int32)
+    out = np.where((prof_table == 0) | (prof_table == 1) | (prof_table == _abi.IMS_PROF_BOX), prof_table, -1).astype(np.int32)
     index = getattr(scene, "sersic_index", None) or {}
     for j, n in enumerate(getattr(scene, "sersic_extra_n", ()) or ()):
         out[prof_table == index[n]] = n_base + n_extra_ktables + j
@@ -156,7 +184,8 @@ def profile_ktable_ids(scene, prof_table, n_extra_ktables=0, n_base=2):
 
 def build_fft_objects(objects, fft_flux, prof_ktable, pixel_scale=0.2):
     """OBJECT_DTYPE rows (geometry as for photon shooting) -> FFT_OBJECT_DTYPE rows, grouped by FFT
-    size.  The profile affine is expressed along the pixel axes: jac' = s * winv * jac."""
+    size.  The profile affine is expressed along the pixel axes: jac' = s * winv * jac.  A box (prof_ktable IMS_PROF_BOX) has its
+    length (prof_scale) and width (prof_aux) folded in, jac' = s * winv * R(pa) * diag(length, width): the kernel sees the unit square."""
     n = len(objects)
     out = np.zeros(n, dtype=FFT_OBJECT_DTYPE)
     size = objects["stamp_xmax"] - objects["stamp_xmin"] + 1
@@ -173,7 +202,10 @@ def build_fft_objects(objects, fft_flux, prof_ktable, pixel_scale=0.2):
     out["cy"] = objects["y0"] - out["y0"]
     out["prof_ktable"] = prof_ktable
     out["prof_scale"] = objects["prof_scale"]
-    w, j = objects["winv"] * pixel_scale, objects["jac"]
+    w, j = objects["winv"] * pixel_scale, np.array(objects["jac"], dtype=np.float64)
+    box = prof_ktable == _abi.IMS_PROF_BOX
+    if box.any():
+        j[box] = j[box] * np.stack([objects["prof_scale"][box], objects["prof_aux"][box]] * 2, axis=1)
     out["jac"] = np.stack([w[:, 0] * j[:, 0] + w[:, 1] * j[:, 2], w[:, 0] * j[:, 1] + w[:, 1] * j[:, 3],
                            w[:, 2] * j[:, 0] + w[:, 3] * j[:, 2], w[:, 2] * j[:, 1] + w[:, 3] * j[:, 3]], axis=1)
     for f in ("stamp_xmin", "stamp_xmax", "stamp_ymin", "stamp_ymax"):

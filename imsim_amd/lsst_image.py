@@ -80,6 +80,8 @@ class LSST_ImageBuilderBase:
             kw["sersic_n"] = sub["sersic_n"]
         if sub.get("mu") is not None:
             kw["jac_det"] = sub["mu"]                        # shear preserves area; the lens magnifies it by mu
+        if sub.get("box_length") is not None:
+            kw["box_area"] = np.asarray(sub["box_length"], dtype=np.float64) * np.asarray(sub["box_width"], dtype=np.float64)
         return fft_draw.use_fft(nominal, sub["kind"], sub["hlr"], fwhm_total, fft_sb_thresh, **kw)
 
     def sky_pixel_areas(self, renderer, use_flux=False):
@@ -268,10 +270,10 @@ class LSST_ImageBuilder(LSST_ImageBuilderBase):
             is_fft = np.zeros(n_all, dtype=bool)
         else:
             is_fft = self._use_fft(sub, nominal, fwhm_total, fft_sb_thresh, kpsf, extra_ktables)
-        is_fft &= np.asarray(sub["kind"]) < 3                  # knots and streaks have no k-space form here: always photons
         objects, sizes = make_objects(sub, np.where(phot > 0, phot, 0))
         keep = np.flatnonzero(phot > 0)                       # SkipThisObject for phot_flux == 0 (stamp.py:199-202)
-        fft_rows = is_fft[keep]
+        # knots and FITS stamps have no k-space form here and stay photon-shot; so does a streak longer than its grid (it would wrap)
+        fft_rows = is_fft[keep] & fft_draw.has_kspace_form(np.asarray(sub["kind"])[keep], objects)
         faint = nominal[keep] < max_flux_simple
         objects["flags"] = np.where(faint, objects["flags"] | IMS_OBJ_FAINT, objects["flags"] & ~IMS_OBJ_FAINT)
         fft_flux = np.zeros(len(objects))
@@ -346,8 +348,9 @@ class LSST_PhotonPoolingImageBuilder(LSST_ImageBuilderBase):
         nominal = np.asarray(sub["nominal_flux"])
         objects, _ = make_objects(sub, phot)
         keep = np.flatnonzero(phot > 0)
-        is_fft = self._use_fft(sub, nominal, fwhm_total, fft_sb_thresh, kpsf, extra_ktables) & (np.asarray(sub["kind"]) < 3)
-        fft_rows = is_fft[keep]
+        is_fft = self._use_fft(sub, nominal, fwhm_total, fft_sb_thresh, kpsf, extra_ktables)
+        # (the same rule as LSST_ImageBuilder.prepare: knots, FITS stamps and streaks longer than their grid stay with the photons)
+        fft_rows = is_fft[keep] & fft_draw.has_kspace_form(np.asarray(sub["kind"])[keep], objects)
         modes = stamp.classify(nominal[keep], max_flux_simple)
         modes[fft_rows] = stamp.ProcessingMode.FFT
         realized = torch.zeros(len(objects), dtype=torch.float64, device=renderer.device)

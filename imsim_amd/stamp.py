@@ -108,7 +108,7 @@ class LSST_SiliconBuilder:
         cat = self._cat
         nominal = np.array([base["nominal_flux"]])
         is_fft = lsst_image.LSST_ImageBuilderBase._use_fft(cat, nominal, self.fwhm_total, self.fft_sb_thresh, self.kpsf, self.extra_ktables)
-        self.use_fft = bool(is_fft[0]) and int(np.asarray(cat["kind"])[0]) < 3
+        self.use_fft = bool(is_fft[0]) and bool(fft_draw.has_kspace_form(np.asarray(cat["kind"])[:1], self._rows[:1])[0])
         if self.use_fft:
             base["fft_flux"], base["phot_flux"] = base["nominal_flux"], 0.0
         return self.kpsf if self.use_fft else None

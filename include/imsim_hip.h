@@ -628,7 +628,9 @@ typedef struct ims_fft_object {
     double  prof_scale;      /* arcsec per k-table unit (half-light radius) */
     double  jac[4];          /* real-space profile affine; the k-vector is transformed by its transpose */
     int32_t nfft;            /* FFT size (even) */
-    int32_t prof_ktable;     /* k-table id of the profile; -1 = DeltaFunction */
+    int32_t prof_ktable;     /* k-table id of the profile; IMS_PROF_POINT (-1) = DeltaFunction; IMS_PROF_BOX (-2) = unit-flux
+                              * galsim.Box: sinc(qx / 2) sinc(qy / 2) at q = jac^T k, length and width folded into jac by the
+                              * host (jac = winv s R(pa) diag(length, width)), prof_scale unused */
     int32_t x0, y0;          /* CCD pixel coordinates of FFT-grid index (0,0) */
     int32_t stamp_xmin, stamp_xmax, stamp_ymin, stamp_ymax;
     int32_t pad[2];
