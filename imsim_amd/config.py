@@ -20,7 +20,7 @@ import numpy as np
 import yaml
 
 from . import _abi, atm_psf, catalog, configs, diffraction, fft_draw, instcat, lsst_image, optical_system, optics as opticsmod
-from . import cosmic_rays, flat, opd as opdmod, parallel, readout, sensor as sensormod, tables, treerings, truth as truthmod, tuning
+from . import cosmic_rays, flat, opd as opdmod, parallel, psf_map as psfmapmod, readout, sensor as sensormod, tables, treerings, truth as truthmod, tuning
 from .engine import Scene, SensorSetup, make_slots
 from .lsst_image import GalSimConfigError
 
@@ -828,7 +828,7 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     if itype not in valid_image_types:
         raise GalSimConfigError(f"Invalid image type {itype}")
     if itype == "LSST_Flat":
-        for k in ("opd", "sag"):                   # a flat has no telescope to trace
+        for k in ("opd", "sag", "psf_map"):        # a flat has no telescope to trace, and no PSF
             if k in out:
                 res.ignored.append(f"output.{k}")
         return _process_flat(cfg, ev, image, res, device, data_dir)
@@ -844,6 +844,8 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     seed = int(ev.value(image.get("random_seed", meta.get("seed", 0))))
     dets = parallel.shard_ccds(range(first, first + nfiles), rank, world)
     opd_kw = parse_opd(out["opd"], ev) if "opd" in out else None     # config errors before any GPU work
+    psf_map_kw = psfmapmod.parse_config(out["psf_map"], ev) if "psf_map" in out else None
+    psf_maps = {}                                                       # file name -> [(cube, header)], one per CCD
     catalogs = parse_catalogs(out, ev, itype)
     crs = parse_cosmic_rays(out, ev, data_dir)
     parse_atm_psf_options(inp.get("atm_psf"), stamp_cfg, ev, data_dir, res, itype, cfg.get("psf"))
@@ -1084,6 +1086,14 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
         img = renderer.image_numpy()                         # the e-image as rendered: the readout chain bleeds the device image in place
         _process_outputs(out, ev, sub, renderer.image, ctx.det_name, meta, ctx.seed_ccd)
         _write_catalogs(catalogs, ev, out, ctx.truth, ctx.cat, ctx.scene.optics.img_wcs, sub)
+        if psf_map_kw is not None:
+            # output.psf_map: the moments of the PSF this CCD was rendered with, on a grid over its pixels (evaluated here, where
+            # det_name and the sequence index are the CCD's)
+            pm = out["psf_map"]
+            fn = os.path.join(str(ev.value(pm.get("dir", out.get("dir", "")))), str(ev.value(pm["file_name"])))
+            wl, thr = tables.synthetic_r_band()
+            psf_maps.setdefault(fn, []).append(psfmapmod.ccd_map(ctx.scene, ctx.det_name, wl_eff=tables.effective_wavelength(wl, thr),
+                                                                 device=device, **psf_map_kw))
         done[ctx.det] = (img, ctx.truth, ctx.det_name, sub)
 
     # Several CCDs of LSST_Image type go through the overlapped focal-plane path (focal_plane.render_focal_plane, the per-CCD
@@ -1125,6 +1135,9 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
         res.eimages += sub.eimages
         res.raw += sub.raw
         res.files += sub.files
+    for fn, hdus in psf_maps.items():                    # one image HDU per CCD that names the file
+        psfmapmod.write(fn, hdus)
+        res.files.append(fn)
     if "sag" in out and rank == 0:
         # the telescope input of the reference holds the camera turned by the rotator (imsim/telescope_loader.py:242-246)
         _process_sag(out["sag"], ev, out, opticsmod.with_camera_rotation(build_telescope(tel_cfg, ev, band),

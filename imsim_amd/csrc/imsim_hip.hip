@@ -442,6 +442,85 @@ __global__ __launch_bounds__(256, (CHAIN == 1) ? IMS_CHAIN_WAVES : IMS_FUSED_WAV
     if (pool.obj_index) pool.obj_index[i] = (int32_t)oi;
 }
 
+// ---------------- PSF moments: the photons reduced instead of landed (ims_psf_moments) ----------------
+// The rows are field points.  Photon k of a row is the photon k_shoot_photons makes for it -- the same device functions on the same
+// Philox counters -- but nothing of it is stored: its weight and its offset from the row's nominal position go into six f64 sums
+// and two counts.  stage 1: after shoot + run_psf, the offset as the PSF kicks leave it (the units of the row's winv; x0, y0 not
+// added).  stage 2: after run_ops as well, position minus (x0, y0).  A photon whose flux is zero (vignetted, or its ray failed)
+// is counted as dropped and adds exact zeros.
+// Every sum is formed in a fixed order: the xor butterfly over the 64 lanes of a wavefront, the four wavefronts of the workgroup
+// in turn through LDS, one record per 256-photon segment; then one workgroup per row adds the row's records -- thread t those of
+// the segments t, t + 256, ... in turn, then the same two steps.  No atomics: a row's result depends on nothing but the row.
+constexpr int PM_N = 8;            // sum w, w x, w y, w x^2, w x y, w y^2, photons used, photons dropped (counts as exact f64 integers)
+
+// the workgroup's totals: thread q < PM_N returns total q, the others 0
+__device__ __forceinline__ double moments_block_sum(double (&v)[PM_N])
+{
+    __shared__ double part[4][PM_N];
+#pragma unroll
+    for (int q = 0; q < PM_N; ++q) v[q] = wave_sum(v[q]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < PM_N; ++q) part[threadIdx.x >> 6][q] = v[q];
+    }
+    __syncthreads();
+    const int q = (int)threadIdx.x;
+    return q < PM_N ? ((part[0][q] + part[1][q]) + part[2][q]) + part[3][q] : 0.0;
+}
+
+template <int CHAIN, int PSF, unsigned long long LAYOUT>
+__global__ __launch_bounds__(256, IMS_FUSED_WAVES) void k_psf_moments(const ims_render_params_t P, const int stage,
+                                                                      double* __restrict__ partial)
+{
+    const int64_t per = (P.n_segments + N_XCD - 1) / N_XCD;
+    const int64_t b = blockIdx.x;
+    if ((b / N_XCD) >= per) return;
+    const int64_t seg = xcd_segment(b, P.n_segments);
+    if (seg >= P.n_segments) return;
+    const int64_t oi = P.seg_object ? (int64_t)P.seg_object[seg] : find_object(P.seg_prefix, P.n_objects, seg);
+    const ims_object_t& o = P.objects[oi];
+    if constexpr (PSF >= 3) optical_setup(P, o);     // the row's optical phase screen, by all 256 threads (ims_optical.h)
+    const int64_t j = (seg - P.seg_prefix[oi]) * P.seg_size + threadIdx.x;
+    double v[PM_N] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    // (the lanes past the row's last photon stay: they hold the zeros of the sums)
+    if (j < o.n_phot) {
+        const int64_t k = o.phot_first + j;
+        Photon ph;
+        Rng rng;
+        rng_reset(rng);
+        shoot(P, o, k, rng, ph);
+        run_psf<PSF>(P, o, k, rng, ph);
+        double dx = ph.x, dy = ph.y;
+        if (stage == 2) {
+            ph.x = o.x0 + ph.x;
+            ph.y = o.y0 + ph.y;
+            run_ops<CHAIN, LAYOUT>(P, o, k, rng, ph);
+            dx = ph.x - o.x0; dy = ph.y - o.y0;
+        }
+        if (ph.flux != 0.0) {
+            const double w = ph.flux, wx = w * dx, wy = w * dy;
+            v[0] = w; v[1] = wx; v[2] = wy; v[3] = wx * dx; v[4] = wx * dy; v[5] = wy * dy; v[6] = 1.0;
+        } else v[7] = 1.0;
+    }
+    const double tot = moments_block_sum(v);
+    if (threadIdx.x < PM_N) partial[seg * PM_N + threadIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void k_psf_moments_combine(const int64_t* __restrict__ seg_prefix, const double* __restrict__ partial,
+                                                             double* __restrict__ sums, int64_t* __restrict__ counts)
+{
+    const int64_t oi = blockIdx.x;
+    const int64_t s0 = seg_prefix[oi], s1 = seg_prefix[oi + 1];
+    double v[PM_N] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    for (int64_t s = s0 + threadIdx.x; s < s1; s += 256) {
+#pragma unroll
+        for (int q = 0; q < PM_N; ++q) v[q] = v[q] + partial[s * PM_N + q];
+    }
+    const double tot = moments_block_sum(v);
+    if (threadIdx.x < 6) sums[oi * 6 + threadIdx.x] = tot;
+    else if (threadIdx.x < PM_N) counts[oi * 2 + (threadIdx.x - 6)] = (int64_t)tot;
+}
+
 __device__ __forceinline__ void load_photon(const ims_photons_t& pool, int64_t i, Photon& ph)
 {
     ph.x = pool.x[i]; ph.y = pool.y[i]; ph.flux = pool.flux[i]; ph.dxdz = pool.dxdz[i]; ph.dydz = pool.dydz[i];
@@ -3631,6 +3710,34 @@ int ims_shoot_ops_photons(const ims_render_params_t* params, const int64_t* phot
             });
         if (rc) return rc;
     }
+    HIP_TRY(hipGetLastError());
+    return IMS_OK;
+}
+
+int ims_psf_moments(const ims_render_params_t* params, int32_t stage, double* partial_dev, double* sums_dev, int64_t* counts_dev,
+                    void* stream)
+{
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (stage != 1 && stage != 2) return set_err(IMS_ERR_ARG, "psf_moments: stage must be 1 (shoot + PSF) or 2 (+ photon operators)");
+    if (params->n_objects == 0) return IMS_OK;
+    if (!sums_dev || !counts_dev) return set_err(IMS_ERR_ARG, "psf_moments: sums / counts is NULL");
+    if (params->n_segments > 0 && !partial_dev) return set_err(IMS_ERR_ARG, "psf_moments: partial is NULL");
+    if (params->n_objects > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "psf_moments: too many points for one call");
+    hipStream_t st = (hipStream_t)stream;
+    if (params->n_segments > 0) {
+        // the kernels of a pool that is not converted (mode 1): the loops over the descriptors, whose photons these are
+        const dim3 grid(grid_for_segments(params->n_segments));
+        const unsigned lds = photon_lds_pad(params);
+        rc = launch_photon_variant<1>(select_photon_variant(params, 1), [&](auto k) {
+            using K = decltype(k);
+            hipLaunchKernelGGL((k_psf_moments<K::chain, K::psf, K::layout>), grid, dim3(256), lds, st, *params, (int)stage, partial_dev);
+        });
+        if (rc) return rc;
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_psf_moments_combine, dim3((unsigned)params->n_objects), dim3(256), 0, st, params->seg_prefix, partial_dev,
+                       sums_dev, counts_dev);
     HIP_TRY(hipGetLastError());
     return IMS_OK;
 }

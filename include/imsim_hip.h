@@ -1099,6 +1099,28 @@ int  ims_trace_field_points_perturbed(const ims_optics_perturbed_t* optics_dev, 
                                       double wave_nm, const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out,
                                       void* stream);
 
+/* ---- moments of the delivered PSF at a table of field points ----
+ * The rows of params->objects are field points: point sources (or any profile) with a position (x0, y0), field angles
+ * (atm_tan_x, atm_tan_y and the DCR terms), an obj_id for the random stream, the first photon phot_first of that stream and a photon
+ * count n_phot; seg_prefix / n_segments / seg_object as for every photon launch.  Photon k of a row is, bit for bit, the photon
+ * ims_shoot_ops_photons stores for the same row, seed and index into a pool that is not converted (the same kernels' device
+ * functions on the same counters), but no photon is stored: per row the launch forms
+ *   sums_dev[6 i ..]   = sum w, sum w x, sum w y, sum w x^2, sum w x y, sum w y^2     (f64; w = the photon's flux)
+ *   counts_dev[2 i ..] = photons with w != 0 (used), photons with w == 0 (dropped: vignetted, or the ray failed)
+ * stage 1: (x, y) is the photon's offset after shoot + the PSF components, as the kicks leave it -- winv applied, (x0, y0) not
+ *          added: arcsec for rows whose winv is the identity.  params->n_ops is not looked at.
+ * stage 2: the photon also runs params->ops[]; (x, y) is its position [pixels of fp_to_pix] minus (x0, y0).  The sensor is
+ *          part of neither stage; params->image may be NULL.
+ * Taking x and y relative to the row's nominal position keeps the sums small against their terms, so that central moments formed
+ * from them on the host do not cancel.  A row with n_phot = 0, or whose photons are all dropped, gets zero sums.
+ * The sums are formed in a fixed order without floating-point atomics (lanes of a wavefront by an xor butterfly, the wavefronts
+ * of a 256-photon segment in turn, the segments of a row by one workgroup in the same way): a row's eight numbers are the same
+ * bits in every call and whatever other rows share the launch, in whatever order.
+ * partial_dev: device scratch of 8 * n_segments doubles (64 B per 256 photons), overwritten.  Added in ABI version 22 without
+ * changing any existing struct or function, so the version number stays. */
+int  ims_psf_moments(const ims_render_params_t* params, int32_t stage, double* partial_dev, double* sums_dev, int64_t* counts_dev,
+                     void* stream);
+
 /* ---- cosmic rays on the e-image (imsim/cosmic_rays.py:paint_cr) ----
  * A footprint of the catalog is a run of spans; a hit paints one footprint (or a run of its spans) at (x0, y0).  Every span
  * pixel lands on image[y0 + row][x0 + col + k] += values[value_offset + k] (k = 0 .. n-1); pixels off the image are dropped.
