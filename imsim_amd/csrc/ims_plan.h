@@ -6,8 +6,8 @@
 // _compile_plan), restated as one native pass so that a CCD of a focal plane costs the host a fraction of a millisecond
 // instead of five.  The Python planner stays as the checker (tests/test_device_table.py, tests/test_parity_gpu.py).
 //
-// Included by imsim_hip.hip inside its extern "C" block's translation unit; uses ims_run_plan, ims_gather_rows and the error
-// helpers defined there.
+// A section of the one translation unit: imsim_hip.hip includes it at file scope, between two of its extern "C" blocks, ahead
+// of the ims_plan_* entry points.  Uses the error helpers of ims_host.h; ims_run_plan and ims_gather_rows run what it builds.
 #pragma once
 
 #include <algorithm>

@@ -6,112 +6,30 @@
 // Segments are dealt to the 8 XCDs in contiguous ranges (block b runs on XCD b%8 on this part),
 // so that objects that are neighbours in the (spatially sorted) table share an XCD's L2 for the
 // pixel-boundary state and the image lines they touch.
+//
+// ONE translation unit, written as sections: ims_host.h (the library's host state and the helpers every entry point uses),
+// this file, then ims_exchange.h and ims_test.h.  A section holds its kernels, its static host helpers and its own extern "C"
+// block, and needs only what is included before it (DESIGN.md has the file map).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
-#include "ims_photon.h"
-#include "ims_fft.h"
-#include "ims_opd.h"
-#include "ims_sed.h"
-
-using namespace ims;
-
-static thread_local char g_err[512] = "";
-static int set_err(int code, const char* msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-static int hip_err(hipError_t e, const char* what)
-{
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return IMS_ERR_HIP;
-}
-// Which of its equivalent kernel forms the library launches is decided by ONE explicit block of settings (ims_tuning_t,
-// include/imsim_hip.h) that the caller may replace with ims_set_tuning -- never by the caller's environment: the library itself
-// reads no environment variable except the file names of the libraries it looks up at run time (csrc/ims_libs.h).
-static ims_tuning_t tuning_defaults()
-{
-    ims_tuning_t t;
-    t.chain_kernels = 1; t.layout_kernels = 1; t.psf_screens_kernel = 1; t.photon_lds = -1;
-    t.round_compact = 1; t.init_tiles = 1; t.upd_dpp = 1; t.joint_lists = 1;
-    t.upd_dpp_max = 128; t.joint_list_min = 1024; t.active_fraction = 0.25;
-    t.round_two_segments = 0; t.joint_fine_marks = 1; t.joint_search_lists = 1; t.pad = 0;
-    return t;
-}
-static ims_tuning_t g_tune = tuning_defaults();
-#define HIP_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_err(e_, #call); } while (0)
-
-// Timing of the dominant kernel: every launch of the selected entry point between ims_enable_timing(which)
-// and the query is bracketed by a hipEvent pair on the launch stream (which: 1 = ims_shoot_accumulate,
-// 2 = ims_shoot_ops_photons, 3 = ims_fft_kspace_fill).
 #include <vector>
 #include <mutex>
 #include <unordered_map>
 #include <map>
 #include <tuple>
-static int g_timing = 0;
-static std::vector<hipEvent_t> g_events;   // pairs
-static size_t g_events_used = 0;
-static std::mutex g_state_mutex;           // the event tables below may be reached from several host threads (focal plane: one per CCD in flight)
+#include "ims_photon.h"
+#include "ims_fft.h"
+#include "ims_opd.h"
+#include "ims_sed.h"
+#include "ims_libs.h"           // hipFFT / RCCL looked up at run time (the handle types the host state names)
 
-struct LaunchTimer {
-    hipStream_t st;
-    size_t slot;
-    bool on;
-    LaunchTimer(hipStream_t s, int which) : st(s), slot(0), on(g_timing == which)
-    {
-        if (on) {
-            hipEvent_t first;
-            {
-                std::lock_guard<std::mutex> lock(g_state_mutex);
-                if (g_events_used + 2 > g_events.size()) {
-                    hipEvent_t a, b;
-                    (void)hipEventCreate(&a); (void)hipEventCreate(&b);
-                    g_events.push_back(a); g_events.push_back(b);
-                }
-                slot = g_events_used;
-                g_events_used += 2;
-                first = g_events[slot];
-                second = g_events[slot + 1];
-            }
-            (void)hipEventRecord(first, st);
-        }
-    }
-    ~LaunchTimer() { if (on) (void)hipEventRecord(second, st); }
-    hipEvent_t second;
-};
+using namespace ims;
 
-// -DIMS_PROBE (measurement builds only, tools/dbg/round_probe.py): the stamps of ims_photon.h's PROBE / PROBE_WG, copied out
-#ifdef IMS_PROBE
-extern "C" int ims_probe_read(unsigned long long* out32, unsigned long long* wg512)
-{
-    if (wg512 && hipMemcpyFromSymbol(wg512, HIP_SYMBOL(ims::g_probe_wg), 512 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    return hipMemcpyFromSymbol(out32, HIP_SYMBOL(ims::g_probe), 32 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
-}
-#endif
-// -DIMS_HIST (measurement builds only, tools/dbg/c5_tile_hist.py): what a listed tile of a joint round holds and costs -- per
-// number of charged cells in the update's 23 x 23 halo (bins 0 .. 62, 63 = more): tiles, 10-ns ticks from the tile's entry to
-// its last store (thread 0), charged cells inside the tile itself
-#ifdef IMS_HIST
-__device__ unsigned long long g_hist[3][64];
-extern "C" int ims_hist_read(unsigned long long* out192, int reset)
-{
-    if (hipMemcpyFromSymbol(out192, HIP_SYMBOL(g_hist), 192 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    if (reset) {
-        static unsigned long long zero[192];
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_hist), zero, sizeof(zero)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
+#include "ims_host.h"           // host state, error / launch helpers, ims_abi_version .. ims_last_kernel_ms, ims_struct_size
 
-#ifdef IMS_EXTRA_LAUNCHES
-__global__ void k_nop(int* p) { if (p) *p = 0; }      // (measurement builds: empty launches on the joint stream -- what a kernel boundary costs a round)
-#endif
 // ---------------- segment -> (object, first photon) ----------------
-constexpr int N_XCD = 8;
 
 __device__ __forceinline__ int64_t xcd_segment(int64_t b, int64_t n_segments)
 {
@@ -858,6 +776,7 @@ struct JointAcc {                           // per chain, constant over the roun
     unsigned int* words[IMS_JOINT_MAX];             // the chain's tile words,
     int32_t first_slot[IMS_JOINT_MAX];              // and the class's first slot
 };
+typedef const JointAcc __attribute__((address_space(4))) * ConstAcc;        // (uniform addresses: scalar loads whatever the kernel stores)
 
 // The tables of ONE round of a joint run -- workgroup ends of the pixel search (ea), tile ends (eu), regions that go on (ns),
 // workgroup ends of the list builder (ewg), tiles per chain (tof) -- live in DEVICE memory, all rounds of the run uploaded at
@@ -883,7 +802,6 @@ __device__ __forceinline__ int joint_entry(const JointEnds* e_global, int c) { r
 
 __device__ __forceinline__ TileListerChain lister_chain(const TileLister& L, int slot_idx)
 {
-    typedef const JointAcc __attribute__((address_space(4))) * ConstAcc;
     ConstAcc Jc = (ConstAcc)(uintptr_t)L.J;
     TileListerChain C;
     C.lo = slot_idx - Jc->first_slot[L.chain];
@@ -902,7 +820,6 @@ __global__ __launch_bounds__(WG, (NV == 8) ? 2 : 4) void k_accumulate_round_j(co
     const int c = joint_chain(&R->ea, b);
     // the table through the CONSTANT address space: its loads at uniform addresses are scalar loads whatever the kernel stores
     // (through a plain pointer the twelve fields sit in vector registers for the whole body: 128 + spills instead of 92)
-    typedef const JointAcc __attribute__((address_space(4))) * ConstAcc;
     ConstAcc Jc = (ConstAcc)(uintptr_t)J;
     ims_render_params_t P;
     ims_photons_t pool;
@@ -3324,89 +3241,7 @@ __global__ __launch_bounds__(256) void k_gather_rows(const ims_object_t* __restr
     ((uint4*)(dst + k))[part] = v;
 }
 
-// device math probe for the parity tests (which: 0 log,1 exp,2 sincos2pi,3 atan,4 sincos,5 tanh,6 gauss,7 dsqrt_n,8 ddiv of pairs,9 dsqrt0)
-__global__ void k_test_math(int which, const double* __restrict__ in, double* __restrict__ out, int64_t n,
-                            uint64_t seed, int64_t obj, uint32_t slot)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double s, c;
-    switch (which) {
-    case 0: out[i] = dlog(in[i]); break;
-    case 1: out[i] = dexp(in[i]); break;
-    case 2: sincos2pi(in[i], s, c); out[2 * i] = s; out[2 * i + 1] = c; break;
-    case 3: out[i] = datan(in[i]); break;
-    case 4: dsincos(in[i], s, c); out[2 * i] = s; out[2 * i + 1] = c; break;
-    case 5: out[i] = dtanh_pos(in[i]); break;
-    case 7: out[i] = dsqrt_n(in[i]); break;
-    case 8: out[i] = ddiv(in[2 * i], in[2 * i + 1]); break;
-    case 9: out[i] = dsqrt0(in[i]); break;
-    case 6: { Rng r; rng_reset(r); rng_block(r, seed, obj, i, slot); gauss_words(r.w[0], r.w[1], s, c);
-              out[2 * i] = s; out[2 * i + 1] = c; break; }
-    // the deviate functions of spec v6; the words come as integer-valued doubles
-    case 10: sincos2pi_w((uint32_t)in[i], s, c); out[2 * i] = s; out[2 * i + 1] = c; break;
-    case 11: out[i] = dlog_w((uint32_t)in[i]); break;
-    case 12: out[i] = gauss_word_cos((uint32_t)in[2 * i], (uint32_t)in[2 * i + 1]); break;
-    }
-}
-
-// the optical phase screen's device functions (ims_optical.h) on n independent points, one thread each: the same functions, in
-// the same order, as optical_setup and apply_psf_optical run them (there a workgroup shares the per-object part through LDS)
-__global__ __launch_bounds__(256) void k_test_optical_screen(const ims_optical_screen_t* __restrict__ screen,
-                                                             const double* __restrict__ thx, const double* __restrict__ thy,
-                                                             const double* __restrict__ u, const double* __restrict__ v, int64_t n,
-                                                             double* __restrict__ coef, double* __restrict__ dwdu,
-                                                             double* __restrict__ dwdv)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    OptScreenPtr S = (OptScreenPtr)screen;
-    const double tx = optical_theta(S, thx[i]), ty = optical_theta(S, thy[i]);
-    double a[IMS_OPT_NZ], gxc[21], gyc[21];
-    for (int j = 0; j < IMS_OPT_NZ; ++j) { a[j] = optical_coeff(S, j, tx, ty); coef[i * IMS_OPT_NZ + j] = a[j]; }
-    for (int t = 0; t < IMS_OPT_NPUPIL; ++t) optical_gradient_coeff(t, optical_pupil_coeff(S, (const double*)a, t), (double*)gxc, (double*)gyc);
-    double gx, gy;
-    optical_gradient((const double*)gxc, (const double*)gyc, S->inv_r, S->grad_scale, u[i], v[i], gx, gy);
-    dwdu[i] = gx; dwdv[i] = gy;
-}
-
 // ---------------- host side of the C-ABI ----------------
-static int check_params(const ims_render_params_t* p)
-{
-    if (!p) return set_err(IMS_ERR_ARG, "params is NULL");
-    if (p->n_objects < 0 || p->n_segments < 0) return set_err(IMS_ERR_ARG, "negative object/segment count");
-    if (p->n_objects > 0 && (!p->objects || !p->seg_prefix)) return set_err(IMS_ERR_ARG, "objects/seg_prefix is NULL");
-    if (p->seg_size != 256) return set_err(IMS_ERR_ARG, "seg_size must be 256 (one photon per thread of a 256-thread workgroup)");
-    if (p->n_psf < 0 || p->n_psf > IMS_MAX_PSF) return set_err(IMS_ERR_ARG, "n_psf out of range");
-    if (p->n_ops < 0 || p->n_ops > IMS_MAX_OPS) return set_err(IMS_ERR_ARG, "n_ops out of range");
-    for (int k = 0; k < p->n_psf; ++k)
-        if (p->psf[k].kind == IMS_PSF_SCREENS && !p->atm) return set_err(IMS_ERR_ARG, "phase-screen PSF without atmosphere descriptor");
-    int n_optical = 0;
-    for (int k = 0; k < p->n_psf; ++k) {
-        if (p->psf[k].kind != IMS_PSF_OPTICAL_SCREEN) continue;
-        if (!p->atm) return set_err(IMS_ERR_ARG, "optical phase screen without its descriptor (atm must point to an ims_atmosphere_optical_t)");
-        if (p->psf[k].chrom_alpha != 0.0) return set_err(IMS_ERR_ARG, "the optical phase screen is achromatic (chrom_alpha must be 0)");
-        if (++n_optical > 1) return set_err(IMS_ERR_ARG, "more than one optical phase screen");
-        // the phase screens address their deviates by their place among the components that are not the optical screen, the
-        // pre-pass (ims_screen_prepass) by their place in the list: the same only while the optical screen comes after them
-        for (int c = k + 1; c < p->n_psf; ++c)
-            if (p->psf[c].kind == IMS_PSF_SCREENS)
-                return set_err(IMS_ERR_ARG, "the optical phase screen must come after the IMS_PSF_SCREENS component (the order of AtmosphericPSF.getPSF)");
-    }
-    for (int k = 0; k < p->n_ops; ++k) {
-        const int kind = p->ops[k].kind;
-        if ((kind == IMS_OP_RUBIN_OPTICS || kind == IMS_OP_RUBIN_DIFFRACTION || kind == IMS_OP_RUBIN_DIFFRACTION_OPTICS) && !p->optics)
-            return set_err(IMS_ERR_ARG, "Rubin optics op without optics descriptor");
-    }
-    return IMS_OK;
-}
-
-static unsigned grid_for_segments(int64_t n_segments)
-{
-    const int64_t per = (n_segments + N_XCD - 1) / N_XCD;
-    return (unsigned)(per * N_XCD);
-}
-
 // ---- which photon kernel a launch gets: one selector, one table of instantiations ----
 static bool has_optical_screen(const ims_render_params_t* p)
 {
@@ -3484,17 +3319,6 @@ static int launch_photon_variant(const PhotonVariant& v, Launch&& launch)
     snprintf(msg, sizeof(msg), "no photon kernel <CHAIN %d, PSF %d, LAYOUT 0x%llx> for mode %d", v.chain, v.psf, v.layout, MODE);
     return set_err(IMS_ERR_UNSUPPORTED, msg);
 }
-
-// f(std::integral_constant<int, NV>) with the vertices per pixel edge as the sensor kernels' template argument: 4, 8, or 0 for
-// the forms that loop over any count
-template <class F>
-static void with_nv(int num_vertices, F&& f)
-{
-    if (num_vertices == 4) f(std::integral_constant<int, 4>{});
-    else if (num_vertices == 8) f(std::integral_constant<int, 8>{});
-    else f(std::integral_constant<int, 0>{});
-}
-
 // what ims_accumulate_segments / _small / _round ask of the pool and the image they deposit it into
 static int check_pooled_accumulate(const ims_render_params_t* params, const ims_photons_t* pool, const int64_t* pool_start)
 {
@@ -3506,73 +3330,6 @@ static int check_pooled_accumulate(const ims_render_params_t* params, const ims_
 }
 
 extern "C" {
-
-int ims_abi_version(void) { return IMS_ABI_VERSION; }
-
-int ims_tuning_defaults(ims_tuning_t* out)
-{
-    if (!out) return set_err(IMS_ERR_ARG, "out is NULL");
-    *out = tuning_defaults();
-    return IMS_OK;
-}
-int ims_get_tuning(ims_tuning_t* out)
-{
-    if (!out) return set_err(IMS_ERR_ARG, "out is NULL");
-    std::lock_guard<std::mutex> lock(g_state_mutex);
-    *out = g_tune;
-    return IMS_OK;
-}
-int ims_set_tuning(const ims_tuning_t* t)
-{
-    if (!t) return set_err(IMS_ERR_ARG, "tuning is NULL");
-    if (t->photon_lds > 65536 - 4096) return set_err(IMS_ERR_ARG, "tuning: photon_lds beyond what a workgroup may ask for");
-    if (t->upd_dpp_max < 0 || t->joint_list_min < 0 || !(t->active_fraction > 0.0) || t->active_fraction > 1.0)
-        return set_err(IMS_ERR_ARG, "tuning: upd_dpp_max / joint_list_min / active_fraction out of range");
-    std::lock_guard<std::mutex> lock(g_state_mutex);
-    g_tune = *t;
-    return IMS_OK;
-}
-const char* ims_last_error(void) { return g_err; }
-
-int ims_device_count(int* count)
-{
-    if (!count) return set_err(IMS_ERR_ARG, "count is NULL");
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) { *count = 0; return hip_err(e, "hipGetDeviceCount"); }
-    *count = n;
-    return IMS_OK;
-}
-
-int ims_device_info(int device, int* n_cu, int* n_xcd, int64_t* lds_bytes, int64_t* hbm_bytes)
-{
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    if (n_cu) *n_cu = prop.multiProcessorCount;
-    if (n_xcd) *n_xcd = N_XCD;
-    if (lds_bytes) *lds_bytes = (int64_t)prop.sharedMemPerMultiprocessor;
-    if (hbm_bytes) *hbm_bytes = (int64_t)prop.totalGlobalMem;
-    return IMS_OK;
-}
-
-int ims_enable_timing(int which) { g_timing = which; g_events_used = 0; return IMS_OK; }
-
-int ims_last_kernel_ms(float* ms, int* n_launches)
-{
-    if (!ms) return set_err(IMS_ERR_ARG, "ms is NULL");
-    if (g_events_used == 0) return set_err(IMS_ERR_ARG, "no timed launch recorded");
-    float total = 0.0f;
-    for (size_t k = 0; k < g_events_used; k += 2) {
-        float t = 0.0f;
-        HIP_TRY(hipEventSynchronize(g_events[k + 1]));
-        HIP_TRY(hipEventElapsedTime(&t, g_events[k], g_events[k + 1]));
-        total += t;
-    }
-    *ms = total;
-    if (n_launches) *n_launches = (int)(g_events_used / 2);
-    g_events_used = 0;
-    return IMS_OK;
-}
 
 int ims_photon_kernel_variant(const ims_render_params_t* params, int32_t mode, int32_t* chain, int32_t* psf, uint64_t* layout)
 {
@@ -3597,11 +3354,6 @@ static unsigned photon_lds_pad(const ims_render_params_t* p)
         if (p->psf[c].kind == IMS_PSF_SCREENS && p->atm != nullptr && p->screen_kick == nullptr) return 41984u;
     return 0u;
 }
-
-// the list of the photons a lazy_static launch sets aside: one buffer per (device, stream), sized for every photon of the launch
-// (launches on a stream run in order, so the next launch finds the second pass of the one before through with it)
-struct MarginBuf { double* list = nullptr; int32_t* count = nullptr; unsigned char* wave_count = nullptr; int64_t waves_cap = 0; uint32_t cap = 0; };
-static std::map<std::pair<int, void*>, MarginBuf> g_margin;
 
 int ims_shoot_accumulate(const ims_render_params_t* params_in, void* stream)
 {
@@ -3830,14 +3582,6 @@ static int accumulate_round_compact(const ims_render_params_t* params, const ims
     return IMS_OK;
 }
 
-static unsigned grid_for_pool(int64_t n)
-{
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
-}
-
 int ims_apply_ops(const ims_render_params_t* params, const int64_t* photon_offset, const ims_photons_t* pool, void* stream)
 {
     int rc = check_params(params);
@@ -3933,7 +3677,44 @@ int ims_sensor_init_boundaries(const ims_sensor_t* sensor_dev, const ims_sensor_
 
 static int update_distortions_impl(const ims_sensor_t* sensor_dev, const ims_sensor_t* sensor_host,
                                    int32_t first_slot, int32_t n_slots, const int64_t* tile_prefix_dev,
-                                   int64_t n_tiles, unsigned char* changed_dev, uint32_t tag, double* fold_image, void* stream);
+                                   int64_t n_tiles, unsigned char* changed_dev, uint32_t tag, double* fold_image, void* stream)
+{
+    if (!sensor_dev) return set_err(IMS_ERR_ARG, "sensor_dev is NULL");
+    if (n_slots == 0) return IMS_OK;
+    if (!tile_prefix_dev || !changed_dev) return set_err(IMS_ERR_ARG, "tile_prefix/changed is NULL");
+    if (sensor_host && sensor_host->qdist > UQMAX) return set_err(IMS_ERR_UNSUPPORTED, "qdist > 4 not supported");
+    int64_t begin, count;
+    int rc = slot_range_cells(sensor_host, first_slot, n_slots, &begin, &count);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (first_slot == 0)                      // slot 0 leaves its pristine state: photons must consult the boundaries again
+        hipLaunchKernelGGL(k_clear_pristine, dim3(1), dim3(1), 0, st, const_cast<ims_sensor_t*>(sensor_dev));
+    const unsigned g = (unsigned)((count + 255) / 256);
+    const int nV = sensor_host ? sensor_host->num_vertices : 0;
+    const int q = sensor_host ? sensor_host->qdist : 0;
+    // The DPP form of the update is the faster one where a round's latency counts (a few tiles: 14.2 -> 11.0 us per launch for
+    // one star), the SGPR form where a launch is throughput work beside the photon kernels (its waves sleep on the scalar
+    // cache instead of pulling 10 KB of table through LDS per tile: C3 25.0 against 25.9 ms): the tile count decides.
+    const bool dpp = sensor_host && sensor_host->bf_dl != nullptr && g_tune.upd_dpp && n_tiles <= g_tune.upd_dpp_max;
+    const dim3 grid((unsigned)n_tiles);
+    with_nv(nV, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        if constexpr (NV != 0) {                                                      // (the q3 update has no form for other counts)
+            if (q == 3) {
+                hipLaunchKernelGGL((dpp ? k_update_distortions_q3<NV, true> : k_update_distortions_q3<NV, false>), grid, dim3(256), 0, st,
+                                   sensor_dev, first_slot, n_slots, tile_prefix_dev, changed_dev, tag, sensor_host->bf_dl);
+                return;
+            }
+        }
+        hipLaunchKernelGGL(k_update_distortions, grid, dim3(256), 0, st, sensor_dev, first_slot, n_slots, tile_prefix_dev, changed_dev, tag);
+    });
+    with_nv(nV, [&](auto nv) {
+        hipLaunchKernelGGL(k_refresh_changed<decltype(nv)::value>, grid, dim3(256), 0, st, sensor_dev, first_slot, n_slots, tile_prefix_dev,
+                           (const unsigned char*)changed_dev, tag, fold_image);
+    });
+    HIP_TRY(hipGetLastError());
+    return IMS_OK;
+}
 
 int ims_sensor_update_distortions(const ims_sensor_t* sensor_dev, const ims_sensor_t* sensor_host,
                                   int32_t first_slot, int32_t n_slots, const int64_t* tile_prefix_dev,
@@ -3985,48 +3766,6 @@ int ims_sensor_fold_delta(const ims_sensor_t* sensor_dev, const ims_sensor_t* se
     HIP_TRY(hipGetLastError());
     return IMS_OK;
 }
-
-static int update_distortions_impl(const ims_sensor_t* sensor_dev, const ims_sensor_t* sensor_host,
-                                   int32_t first_slot, int32_t n_slots, const int64_t* tile_prefix_dev,
-                                   int64_t n_tiles, unsigned char* changed_dev, uint32_t tag, double* fold_image, void* stream)
-{
-    if (!sensor_dev) return set_err(IMS_ERR_ARG, "sensor_dev is NULL");
-    if (n_slots == 0) return IMS_OK;
-    if (!tile_prefix_dev || !changed_dev) return set_err(IMS_ERR_ARG, "tile_prefix/changed is NULL");
-    if (sensor_host && sensor_host->qdist > UQMAX) return set_err(IMS_ERR_UNSUPPORTED, "qdist > 4 not supported");
-    int64_t begin, count;
-    int rc = slot_range_cells(sensor_host, first_slot, n_slots, &begin, &count);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (first_slot == 0)                      // slot 0 leaves its pristine state: photons must consult the boundaries again
-        hipLaunchKernelGGL(k_clear_pristine, dim3(1), dim3(1), 0, st, const_cast<ims_sensor_t*>(sensor_dev));
-    const unsigned g = (unsigned)((count + 255) / 256);
-    const int nV = sensor_host ? sensor_host->num_vertices : 0;
-    const int q = sensor_host ? sensor_host->qdist : 0;
-    // The DPP form of the update is the faster one where a round's latency counts (a few tiles: 14.2 -> 11.0 us per launch for
-    // one star), the SGPR form where a launch is throughput work beside the photon kernels (its waves sleep on the scalar
-    // cache instead of pulling 10 KB of table through LDS per tile: C3 25.0 against 25.9 ms): the tile count decides.
-    const bool dpp = sensor_host && sensor_host->bf_dl != nullptr && g_tune.upd_dpp && n_tiles <= g_tune.upd_dpp_max;
-    const dim3 grid((unsigned)n_tiles);
-    with_nv(nV, [&](auto nv) {
-        constexpr int NV = decltype(nv)::value;
-        if constexpr (NV != 0) {                                                      // (the q3 update has no form for other counts)
-            if (q == 3) {
-                hipLaunchKernelGGL((dpp ? k_update_distortions_q3<NV, true> : k_update_distortions_q3<NV, false>), grid, dim3(256), 0, st,
-                                   sensor_dev, first_slot, n_slots, tile_prefix_dev, changed_dev, tag, sensor_host->bf_dl);
-                return;
-            }
-        }
-        hipLaunchKernelGGL(k_update_distortions, grid, dim3(256), 0, st, sensor_dev, first_slot, n_slots, tile_prefix_dev, changed_dev, tag);
-    });
-    with_nv(nV, [&](auto nv) {
-        hipLaunchKernelGGL(k_refresh_changed<decltype(nv)::value>, grid, dim3(256), 0, st, sensor_dev, first_slot, n_slots, tile_prefix_dev,
-                           (const unsigned char*)changed_dev, tag, fold_image);
-    });
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
 
 // library events of RECORD / WAIT items (one process per GPU)
 static int plan_event(int number, hipEvent_t* out)
@@ -4273,24 +4012,7 @@ int ims_plan_upload(void* plan, void* stream)
 
 static int plan_enqueue(ims_planner::Plan* pl, ims_sensor_t* sensor_dev, ims_sensor_t* sensor_host, ims_bf_slot_t* slots_dev,
                         unsigned char* changed_dev, void* main_stream, void* const* streams, int32_t n_streams, int32_t own_work_queued,
-                        bool defer_top = false);
-
-// (Two other forms of this call were built, measured in round 4 and removed in round 5: the whole enqueue captured into a
-// hipGraph -- capture + instantiate + launch of a CCD's ~3 000-node plan cost the host 51 ms against 24 ms for enqueueing it, and a
-// graph does not run on the caller's streams -- and one plan's rounds through the joint runner with its tile lists -- a fourth
-// dependent launch per round on a chain of 185 rounds: C3 24.2 -> 25.2 ms without lists, 33 ms with them.)
-int ims_plan_run(void* plan, ims_sensor_t* sensor_dev, ims_sensor_t* sensor_host, ims_bf_slot_t* slots_dev, unsigned char* changed_dev,
-                 void* main_stream, void* const* streams, int32_t n_streams, int32_t own_work_queued)
-{
-    using namespace ims_planner;
-    Plan* pl = (Plan*)plan;
-    if (!pl || !pl->uploaded) return set_err(IMS_ERR_ARG, "plan is NULL or not uploaded");
-    return plan_enqueue(pl, sensor_dev, sensor_host, slots_dev, changed_dev, main_stream, streams, n_streams, own_work_queued);
-}
-
-static int plan_enqueue(ims_planner::Plan* pl, ims_sensor_t* sensor_dev, ims_sensor_t* sensor_host, ims_bf_slot_t* slots_dev,
-                        unsigned char* changed_dev, void* main_stream, void* const* streams, int32_t n_streams, int32_t own_work_queued,
-                        bool defer_top)
+                        bool defer_top = false)
 {
     using namespace ims_planner;
     if (!streams || n_streams < 5) return set_err(IMS_ERR_ARG, "streams: five plan streams by role are required");
@@ -4373,6 +4095,19 @@ static int plan_enqueue(ims_planner::Plan* pl, ims_sensor_t* sensor_dev, ims_sen
         HIP_TRY(hipStreamWaitEvent(main, pl->events[2 + uniq.size() + k], 0));
     }
     return IMS_OK;
+}
+
+// (Two other forms of this call were built, measured in round 4 and removed in round 5: the whole enqueue captured into a
+// hipGraph -- capture + instantiate + launch of a CCD's ~3 000-node plan cost the host 51 ms against 24 ms for enqueueing it, and a
+// graph does not run on the caller's streams -- and one plan's rounds through the joint runner with its tile lists -- a fourth
+// dependent launch per round on a chain of 185 rounds: C3 24.2 -> 25.2 ms without lists, 33 ms with them.)
+int ims_plan_run(void* plan, ims_sensor_t* sensor_dev, ims_sensor_t* sensor_host, ims_bf_slot_t* slots_dev, unsigned char* changed_dev,
+                 void* main_stream, void* const* streams, int32_t n_streams, int32_t own_work_queued)
+{
+    using namespace ims_planner;
+    Plan* pl = (Plan*)plan;
+    if (!pl || !pl->uploaded) return set_err(IMS_ERR_ARG, "plan is NULL or not uploaded");
+    return plan_enqueue(pl, sensor_dev, sensor_host, slots_dev, changed_dev, main_stream, streams, n_streams, own_work_queued);
 }
 
 int ims_plan_join(void* plan, void* stream)
@@ -4669,38 +4404,13 @@ int ims_plan_add_realized(void* plan, double* out_dev, void* stream)
     return IMS_OK;
 }
 
-// ---- the inverse transforms of the FFT branch (hipFFT, plans cached) and the exchanges between GPUs (RCCL) ----
 }  // extern "C"
-#include "ims_libs.h"
 
+// ---- the inverse transforms of the FFT branch (hipFFT, plans cached) ----
 __global__ __launch_bounds__(256) void k_scale(double* __restrict__ v, int64_t n, double s)
 {
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) v[i] = v[i] * s;
-}
-
-__global__ __launch_bounds__(256) void k_f64_to_i32(const double* __restrict__ src, int32_t* __restrict__ dst, int64_t n)
-{
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) dst[i] = (int32_t)src[i];
-}
-
-__global__ __launch_bounds__(256) void k_i32_to_f64(const int32_t* __restrict__ src, double* __restrict__ dst, int64_t n)
-{
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) dst[i] = (double)src[i];
-}
-
-// not an integer count below 2^31 / world: the int32 exchange would not be exact for it
-__global__ __launch_bounds__(256) void k_count_inexact(const double* __restrict__ src, int64_t n, double limit, unsigned long long* __restrict__ bad)
-{
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    unsigned long long c = 0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const double v = src[i];
-        if (!(v >= 0.0 && v < limit && v == floor(v))) ++c;
-    }
-    if (c) atomicAdd(bad, c);
 }
 
 extern "C" {
@@ -4722,8 +4432,6 @@ static int fft_err(hipfftResult r, const char* what)
 // objects of two CCDs of a focal plane on the two top-chain streams -- would share it.  Small transforms (below 1024^2:
 // launch-bound) keep batched plans.  ims_fft_warm makes the plans ahead of time (from another host thread, while the host
 // still reads catalogs).
-static std::mutex g_fft_mutex;
-static std::map<std::tuple<int32_t, int64_t, void*>, hipfftHandle> g_fft_plans;
 
 // the plan of (nfft, per_plan, stream): looked up under the lock, MADE outside it (seconds for a size's first plan: plans of
 // different sizes are made side by side by ims_fft_warm's callers), entered under the lock again
@@ -4805,107 +4513,6 @@ int ims_fft_inverse(double* kbuf_dev, double* rbuf_dev, int32_t nfft, int64_t ba
 int ims_fft_inverse_raw(double* kbuf_dev, double* rbuf_dev, int32_t nfft, int64_t batch, void* stream)
 {
     return fft_inverse_impl(kbuf_dev, rbuf_dev, nfft, batch, stream, false);
-}
-
-// ---- exchanges between the GPUs of a node (RCCL over xGMI) ----
-static int nccl_err(ncclResult_t r, const char* what)
-{
-    if (r == ncclSuccess) return IMS_OK;
-    const ims_libs::Rccl* R = ims_libs::rccl();
-    char buf[384];
-    snprintf(buf, sizeof(buf), "%s: %s", what, R ? R->error_string(r) : "rccl error");
-    return set_err(IMS_ERR_HIP, buf);
-}
-
-struct ImsComm { ncclComm_t comm; int32_t rank, world; };
-
-int ims_comm_unique_id(void* id128)
-{
-    if (!id128) return set_err(IMS_ERR_ARG, "id128 is NULL");
-    const ims_libs::Rccl* R = ims_libs::rccl();
-    if (!R) return set_err(IMS_ERR_UNSUPPORTED, "RCCL is not loadable (librccl.so; IMS_RCCL_LIB names a file)");
-    static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId");
-    return nccl_err(R->get_unique_id((ncclUniqueId*)id128), "ncclGetUniqueId");
-}
-
-int ims_comm_init(const void* id128, int32_t rank, int32_t world, void** comm_out)
-{
-    if (!id128 || !comm_out || world < 1 || rank < 0 || rank >= world) return set_err(IMS_ERR_ARG, "id / comm_out / rank / world");
-    const ims_libs::Rccl* R = ims_libs::rccl();
-    if (!R) return set_err(IMS_ERR_UNSUPPORTED, "RCCL is not loadable (librccl.so; IMS_RCCL_LIB names a file)");
-    ncclUniqueId id;
-    std::memcpy(&id, id128, sizeof(id));
-    ncclComm_t c = nullptr;
-    const int rc = nccl_err(R->comm_init_rank(&c, world, id, rank), "ncclCommInitRank");
-    if (rc) return rc;
-    *comm_out = new ImsComm{ c, rank, world };
-    return IMS_OK;
-}
-
-int ims_comm_destroy(void* comm)
-{
-    if (!comm) return IMS_OK;
-    const ims_libs::Rccl* R = ims_libs::rccl();
-    if (!R) return set_err(IMS_ERR_UNSUPPORTED, "RCCL is not loadable");
-    ImsComm* ic = (ImsComm*)comm;
-    const int rc = nccl_err(R->comm_destroy(ic->comm), "ncclCommDestroy");
-    delete ic;
-    return rc;
-}
-
-static unsigned exchange_grid(int64_t n)
-{
-    int64_t b = (n + 255) / 256;
-    return (unsigned)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
-}
-
-int ims_count_inexact(const double* image_dev, int64_t n, int32_t world, unsigned long long* bad_dev, void* stream)
-{
-    if (!image_dev || !bad_dev || n < 0 || world < 1) return set_err(IMS_ERR_ARG, "NULL / negative argument");
-    if (n == 0) return IMS_OK;
-    hipLaunchKernelGGL(k_count_inexact, dim3(exchange_grid(n)), dim3(256), 0, (hipStream_t)stream, image_dev, n,
-                       2147483648.0 / (double)world, bad_dev);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-// sum of the ranks' images onto `root` (in place there; the other ranks' images are left as they are), or onto every rank
-static int exchange(void* comm, double* image_dev, int32_t* scratch_i32_dev, int64_t n, int32_t root, int32_t integer_counts, void* stream)
-{
-    if (!comm || !image_dev || n < 0) return set_err(IMS_ERR_ARG, "comm / image is NULL");
-    if (integer_counts && !scratch_i32_dev) return set_err(IMS_ERR_ARG, "scratch_i32_dev is NULL");
-    if (n == 0) return IMS_OK;
-    const ims_libs::Rccl* R = ims_libs::rccl();
-    if (!R) return set_err(IMS_ERR_UNSUPPORTED, "RCCL is not loadable");
-    hipStream_t st = (hipStream_t)stream;
-    const ImsComm* ic = (const ImsComm*)comm;
-    ncclComm_t c = ic->comm;
-    if (root >= ic->world) return set_err(IMS_ERR_ARG, "root out of range");
-    if (integer_counts) {
-        // unit photon fluxes: every pixel is an integer count, exchanged as int32 -- half the bytes on the per-link-bound ring, and
-        // still exact (the caller checks the counts against 2^31 / world once: ims_count_inexact)
-        hipLaunchKernelGGL(k_f64_to_i32, dim3(exchange_grid(n)), dim3(256), 0, st, (const double*)image_dev, scratch_i32_dev, n);
-        const int rc = root >= 0 ? nccl_err(R->reduce(scratch_i32_dev, scratch_i32_dev, (size_t)n, ncclInt32, ncclSum, root, c, st), "ncclReduce")
-                                 : nccl_err(R->all_reduce(scratch_i32_dev, scratch_i32_dev, (size_t)n, ncclInt32, ncclSum, c, st), "ncclAllReduce");
-        if (rc) return rc;
-        if (root < 0 || root == ic->rank)          // a reduce leaves the other ranks' images as they were
-            hipLaunchKernelGGL(k_i32_to_f64, dim3(exchange_grid(n)), dim3(256), 0, st, (const int32_t*)scratch_i32_dev, image_dev, n);
-        HIP_TRY(hipGetLastError());
-        return IMS_OK;
-    }
-    return root >= 0 ? nccl_err(R->reduce(image_dev, image_dev, (size_t)n, ncclFloat64, ncclSum, root, c, st), "ncclReduce")
-                     : nccl_err(R->all_reduce(image_dev, image_dev, (size_t)n, ncclFloat64, ncclSum, c, st), "ncclAllReduce");
-}
-
-int ims_reduce_image(void* comm, double* image_dev, int32_t* scratch_i32_dev, int64_t n, int32_t root, int32_t integer_counts, void* stream)
-{
-    if (root < 0) return set_err(IMS_ERR_ARG, "root must be >= 0");
-    return exchange(comm, image_dev, scratch_i32_dev, n, root, integer_counts, stream);
-}
-
-int ims_allreduce_delta(void* comm, double* delta_dev, int32_t* scratch_i32_dev, int64_t n, int32_t integer_counts, void* stream)
-{
-    return exchange(comm, delta_dev, scratch_i32_dev, n, -1, integer_counts, stream);
 }
 
 // a workgroup's share of the elements of an elementwise FFT kernel (walk_span): at least 4 096 workgroups where the elements allow it
@@ -5483,43 +5090,6 @@ int64_t ims_parse_instcat_objects(const char* text, int64_t n_bytes, int64_t max
     return n_out;
 }
 
-int ims_struct_size(int which)
-{
-    switch (which) {
-    case 0: return (int)sizeof(ims_object_t);
-    case 1: return (int)sizeof(ims_radial_tables_t);
-    case 2: return (int)sizeof(ims_lin_tables_t);
-    case 3: return (int)sizeof(ims_psf_component_t);
-    case 4: return (int)sizeof(ims_op_t);
-    case 5: return (int)sizeof(ims_surface_t);
-    case 6: return (int)sizeof(ims_tansip_t);
-    case 7: return (int)sizeof(ims_optics_t);
-    case 8: return (int)sizeof(ims_bf_slot_t);
-    case 9: return (int)sizeof(ims_sensor_t);
-    case 10: return (int)sizeof(ims_photons_t);
-    case 11: return (int)sizeof(ims_render_params_t);
-    case 12: return (int)sizeof(ims_plan_item_t);
-    case 13: return (int)sizeof(ims_atmosphere_t);
-    case 14: return (int)sizeof(ims_fft_object_t);
-    case 15: return (int)sizeof(ims_fft_params_t);
-    case 16: return (int)sizeof(ims_readout_t);
-    case 17: return (int)sizeof(ims_chain_t);
-    case 18: return (int)sizeof(ims_catalog_t);
-    case 19: return (int)sizeof(ims_object_meta_t);
-    case 20: return (int)sizeof(ims_plan_input_t);
-    case 21: return (int)sizeof(ims_plan_sizes_t);
-    case 22: return (int)sizeof(ims_tuning_t);
-    case 23: return (int)sizeof(ims_opd_t);
-    case 24: return (int)sizeof(ims_optics_perturbed_t);
-    case 25: return (int)sizeof(ims_perturbation_t);
-    case 26: return (int)sizeof(ims_cr_span_t);
-    case 27: return (int)sizeof(ims_cr_hit_t);
-    case 28: return (int)sizeof(ims_optical_screen_t);
-    case 29: return (int)sizeof(ims_atmosphere_optical_t);
-    }
-    return -1;
-}
-
 static int opd_run(const ims_opd_t* P, const ims_optics_t* optics_dev, bool pert, void* stream)
 {
     if (!P || !optics_dev) return set_err(IMS_ERR_ARG, "opd / optics is NULL");
@@ -5601,25 +5171,7 @@ int ims_trace_field_points_perturbed(const ims_optics_perturbed_t* optics_dev, c
                                   ngood_out, stream);
 }
 
-int ims_test_math(int which, const double* in_dev, double* out_dev, int64_t n, uint64_t seed, int64_t obj,
-                  uint32_t slot, void* stream)
-{
-    if (n <= 0) return IMS_OK;
-    hipLaunchKernelGGL(k_test_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       which, in_dev, out_dev, n, seed, obj, slot);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_test_optical_screen(const ims_optical_screen_t* screen_dev, const double* thx, const double* thy, const double* u,
-                            const double* v, int64_t n, double* coef, double* dwdu, double* dwdv, void* stream)
-{
-    if (n <= 0) return IMS_OK;
-    if (!screen_dev || !thx || !thy || !u || !v || !coef || !dwdu || !dwdv) return set_err(IMS_ERR_ARG, "optical screen probe: NULL argument");
-    hipLaunchKernelGGL(k_test_optical_screen, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       screen_dev, thx, thy, u, v, n, coef, dwdu, dwdv);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
 }  // extern "C"
+
+#include "ims_exchange.h"       // RCCL exchanges between the GPUs of a node
+#include "ims_test.h"           // device probes of the parity tests

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static check of the hand-written DPP instructions in the gfx950 assembly of csrc/imsim_hip.hip.
+"""Static check of the hand-written DPP instructions in the gfx950 assembly of csrc/imsim_hip.hip
+(the translation unit with its sections csrc/ims_*.h; the DPP forms are fmac_bcast and update_tile_q3_dpp in the file itself).
 
 The compiler's hazard recogniser does not look inside inline asm.  gfx9 needs two wait states between a VALU instruction
 that writes a VGPR and a DPP instruction that reads that VGPR as its DPP source (src0), and five between a VALU write of

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Register / scratch / LDS / occupancy table of every kernel in csrc/imsim_hip.hip.
+"""Register / scratch / LDS / occupancy table of every kernel in csrc/imsim_hip.hip (one translation unit: the file
+includes its sections csrc/ims_*.h, which define kernels too; DESIGN.md section 4 has the file map).
 
 Compiles the translation unit for gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints
 one line per kernel.  Usage: python tools/kernel_resources.py [extra hipcc flags ...]"""
