@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _abi, tables, tuning
 from ._abi import FFT_OBJECT_DTYPE, FftParams, KPsf
-from .catalog import KIND_STREAK
+from .catalog import KIND_KNOTS, KIND_STREAK
 
 KOLMOGOROV_K0 = 2.992934 * 0.9758634299       # k0 * fwhm for exp(-(k/k0)^(5/3))  [rad/arcsec * arcsec]
 
@@ -104,13 +104,17 @@ def kpsf_peak_per_flux(kpsf, ktables=None, q_step=None, n_base=2):
 
 
 def max_surface_brightness(flux, kind, hlr, fwhm_total=None, pixel_scale=0.2, sersic_n=None, jac_det=None, psf_peaks=None,
-                           box_area=None):
+                           box_area=None, fft_knots=False):
     """`Convolve(gal_achrom, fft_psf).withFlux(F).max_sb / 2 * pixel_scale^2` [photons/pixel], the quantity
     get_fft_psf_maybe compares with fft_sb_thresh (imsim/psf_utils.py:201-212).  GalSim's max_sb of a convolution is the
     estimate that is exact for Gaussians: F / sum_i (1 / peak_i) with peak_i the central surface brightness per unit
     flux of component i (a DeltaFunction contributes nothing).  Sersic: b^2n / (2 pi n Gamma(2n) hlr^2 |det J|).
     Streak (galsim.Box): 1 / (length width), Box.max_sb per unit flux, with box_area = length x width [arcsec^2] per object.
-    psf_peaks: kpsf_peak_per_flux of the FFT-mode PSF; without it a single Gaussian of FWHM fwhm_total stands in."""
+    psf_peaks: kpsf_peak_per_flux of the FFT-mode PSF; without it a single Gaussian of FWHM fwhm_total stands in.
+    fft_knots (stamp.fft_knots, off by default): RandomKnots counts as GalSim counts it -- a sum of DeltaFunctions, each of which adds
+    nothing to the convolution's estimate (galsim/convolve.py, Convolution.max_sb: the sum of flux / max_sb over the components, to
+    which a delta function adds 0), so the estimate is the PSF's alone, as for a point source.  (Stated from GalSim's source: GalSim is
+    not installed where this was written, so no call confirms it.)  Off: knots get no estimate and stay photon-shot."""
     from scipy import special
     flux = np.asarray(flux, dtype=np.float64)
     kind = np.asarray(kind)
@@ -135,20 +139,27 @@ def max_surface_brightness(flux, kind, hlr, fwhm_total=None, pixel_scale=0.2, se
     if box.any():
         inv[box] = inv[box] + np.broadcast_to(np.asarray(box_area, dtype=np.float64), kind.shape)[box]
     other = (~gal) & (~box) & (kind != 0)   # knots and FITS images have no k-space form here: a broad stand-in keeps them photon-shot
+    if fft_knots:
+        other &= kind != KIND_KNOTS         # (knots behind stamp.fft_knots: the PSF's estimate alone, as for kind 0)
     inv[other] = np.inf
     return flux / inv / 2.0 * pixel_scale ** 2
 
 
-def has_kspace_form(kind, objects=None, pixel_scale=0.2):
+def has_kspace_form(kind, objects=None, pixel_scale=0.2, fft_knots=False, n_alias=0):
     """Which objects the FFT branch can draw at all: points, Sersic profiles and streaks (galsim.Box).  RandomKnots and FITS-image
     objects have no k-space form here and stay photon-shot whatever their flux.  So does a streak that does not fit the periodic
     grid its stamp gives it (objects: the OBJECT_DTYPE rows, same length as kind) -- a good stamp size capped at catalog.NMAX, or a
     stamp size given by the user, can be shorter than the trail, which would then wrap round the grid, where GalSim raises
     GalSimFFTSizeError.  Deliberate: the trail is still drawn, by photons.  The test is on the box's extent along the pixel axes,
-    |J| (length, width) with J = s winv R(pa), against nfft * pixel_scale."""
+    |J| (length, width) with J = s winv R(pa), against nfft * pixel_scale.
+    fft_knots (stamp.fft_knots, off by default): RandomKnots has a k-space form too -- the point's spectrum times the structure factor
+    of its knots (ims_fft_knots_factor) -- but only in the base band: with n_alias > 0 (alias_order of the FFT-mode PSF) the structure
+    factor is no common factor of the folded sum, and knots stay photon-shot."""
     kind = np.asarray(kind)
     box = kind == KIND_STREAK
     ok = (kind < 3) | box
+    if fft_knots and n_alias <= 0:
+        ok = ok | (kind == KIND_KNOTS)
     if objects is not None and box.any():
         o = objects[box]
         size = o["stamp_xmax"] - o["stamp_xmin"] + 1                    # the grid build_fft_objects will take
@@ -161,13 +172,13 @@ def has_kspace_form(kind, objects=None, pixel_scale=0.2):
     return ok
 
 
-def use_fft(nominal_flux, kind, hlr, fwhm_total, fft_sb_thresh, **kw):
-    """The FFT-vs-phot decision of LSST_SiliconBuilder.buildPSF (stamp.py:275-308)."""
+def use_fft(nominal_flux, kind, hlr, fwhm_total, fft_sb_thresh, fft_knots=False, **kw):
+    """The FFT-vs-phot decision of LSST_SiliconBuilder.buildPSF (stamp.py:275-308).  fft_knots: see max_surface_brightness."""
     nominal_flux = np.asarray(nominal_flux, dtype=np.float64)
     if not fft_sb_thresh:
         return np.zeros(nominal_flux.shape, dtype=bool)
     cand = (nominal_flux >= 1.0e6) & (nominal_flux >= fft_sb_thresh)
-    return cand & (max_surface_brightness(nominal_flux, kind, hlr, fwhm_total, **kw) > fft_sb_thresh)
+    return cand & (max_surface_brightness(nominal_flux, kind, hlr, fwhm_total, fft_knots=fft_knots, **kw) > fft_sb_thresh)
 
 
 def profile_ktable_ids(scene, prof_table, n_extra_ktables=0, n_base=2):
@@ -214,6 +225,34 @@ def build_fft_objects(objects, fft_flux, prof_ktable, pixel_scale=0.2):
     out["k_offset"] = np.concatenate([[0], np.cumsum(nfft.astype(np.int64) * nh)])[:-1]
     out["r_offset"] = np.concatenate([[0], np.cumsum(nfft.astype(np.int64) ** 2)])[:-1]
     return out, order
+
+
+def knot_side_arrays(objects, order):
+    """The side arrays of ims_knot_positions / ims_fft_knots_factor for the OBJECT_DTYPE rows that build_fft_objects turned into FFT
+    rows, in the order of those rows (`order`: build_fft_objects's second result): n_knots (int32; 0 for everything that is not a
+    RandomKnots object), sigma (the photon row's prof_scale: the Gaussian sigma of the knots' parent profile) and knot_offset (int64:
+    the exclusive prefix sum of n_knots).  No struct gains a field."""
+    o = np.asarray(objects)[np.asarray(order)]
+    n_knots = np.where(o["prof_table"] == _abi.IMS_PROF_KNOTS, o["prof_aux"], 0.0).astype(np.int32)
+    sigma = np.where(n_knots > 0, o["prof_scale"], 0.0).astype(np.float64)
+    offset = np.concatenate([[0], np.cumsum(n_knots, dtype=np.int64)])[:-1].astype(np.int64)
+    return n_knots, sigma, offset
+
+
+def kpsf_alias_order(kpsf, extra_ktables=(), n_base=2, pixel_scale=0.2):
+    """alias_order of a k-space PSF as FftDrawer will find it (ims_fft_params_t.n_alias), from the PSF's own k-tables alone: the
+    profile tables in front of them (n_base) are not looked at by a PSF component."""
+    q_step = tables.KTABLE_QMAX / (tables.KTABLE_NPTS - 1)
+    if not kpsf:
+        return 0
+    t = np.stack([np.zeros(tables.KTABLE_NPTS)] * n_base + [np.asarray(x, dtype=np.float64) for x in extra_ktables])
+    return alias_order(kpsf, t, q_step, pixel_scale)
+
+
+class DrawState(tuple):
+    """what FftDrawer._upload hands to _run: (rows, obj_t, nfft, kpre, rpre, kpre_t, rpre_t, kbuf, rbuf), and in `knots` the device
+    side of a batch's RandomKnots objects (None: the batch has none)"""
+    knots = None
 
 
 def set_spikes(P, diffraction_fft, wavelength, renderer=None):
@@ -393,19 +432,20 @@ class FftDrawer:
         self.P, self._keep = fft_params(renderer.scene, kpsf, np.stack([t[1] for t in tabs] + list(extra_ktables) + more), self.q_step,
                                         renderer.scene.seed, add_noise, lambda a: renderer.mem.put(a, np.float64))
         self.P.image = renderer.image.data_ptr()
+        self.knot_launches = 0                  # draws that ran the structure-factor pass (a batch without RandomKnots launches nothing)
         set_spikes(self.P, diffraction_fft, wavelength, renderer)
 
-    def draw(self, fft_objects, realized=None):
+    def draw(self, fft_objects, realized=None, knots=None):
         """fft_objects: FFT_OBJECT_DTYPE rows sorted by nfft (build_fft_objects).  `realized`:
-        optional float64 device tensor [n]."""
+        optional float64 device tensor [n].  knots: knot_side_arrays of the rows (stamp.fft_knots), None without RandomKnots objects."""
         if len(fft_objects) == 0:
             return
-        return self._run(self._upload(fft_objects), realized)
+        return self._run(self._upload(fft_objects, knots), realized)
 
-    def prepared(self, fft_objects):
+    def prepared(self, fft_objects, knots=None):
         """Upload the rows and allocate the k-space / real-space buffers once; returns a zero-argument callable that
         draws the batch (bench.py: the timed region starts with its inputs resident in HBM)."""
-        state = self._upload(fft_objects)
+        state = self._upload(fft_objects, knots)
 
         def launch():
             self._run(state, None)
@@ -464,7 +504,7 @@ class FftDrawer:
         launch.keep = (states, kbuf, rbuf, spike)
         return launch
 
-    def _upload(self, fft_objects):
+    def _upload(self, fft_objects, knots=None):
         torch, r = self.torch, self.r
         rows = np.ascontiguousarray(fft_objects, dtype=FFT_OBJECT_DTYPE)
         from .engine import upload_async
@@ -480,7 +520,33 @@ class FftDrawer:
         self._spike_bufs = ((torch.empty_like(rbuf), torch.empty(4 * len(rows), dtype=torch.int32, device=r.device))
                             if self.P.spikes.enabled else None)
         self._spike_list = self._make_spike_list(int(rpre[-1])) if self.P.spikes.enabled else None
-        return rows, obj_t, nfft, kpre, rpre, kpre_t, rpre_t, kbuf, rbuf
+        state = DrawState((rows, obj_t, nfft, kpre, rpre, kpre_t, rpre_t, kbuf, rbuf))
+        if knots is not None and np.any(np.asarray(knots[0]) > 0):
+            state.knots = self._upload_knots(rows, knots)
+        return state
+
+    def _upload_knots(self, rows, knots):
+        """the side arrays of a batch's RandomKnots objects on the device, the list of their rows and the buffer of the knots'
+        displacements (ims_knot_positions fills it in _run)"""
+        torch, r = self.torch, self.r
+        from .engine import upload_async
+        if self.P.n_alias > 0:
+            raise ValueError("RandomKnots on the FFT branch needs a PSF without aliases to fold (n_alias == 0): fft_draw.has_kspace_form "
+                             "keeps such objects photon-shot")
+        n_knots = np.ascontiguousarray(knots[0], dtype=np.int32)
+        sigma = np.ascontiguousarray(knots[1], dtype=np.float64)
+        offset = np.ascontiguousarray(knots[2], dtype=np.int64)
+        if not (len(n_knots) == len(sigma) == len(offset) == len(rows)):
+            raise ValueError("knots: one entry per FFT row")
+        if (n_knots < 0).any() or not np.array_equal(offset, np.concatenate([[0], np.cumsum(n_knots, dtype=np.int64)])[:-1]):
+            raise ValueError("knots: knot_offset must be the exclusive prefix sum of n_knots >= 0")
+        which = np.flatnonzero(n_knots > 0).astype(np.int32)
+        if (rows["prof_ktable"][which] != _abi.IMS_PROF_POINT).any():
+            raise ValueError("knots: a RandomKnots row is filled as a point (prof_ktable -1)")
+        return dict(n_rows=len(which), max_nfft=int(rows["nfft"][which].max()), n_knots=upload_async(torch, r.device, n_knots),
+                    sigma=upload_async(torch, r.device, sigma), offset=upload_async(torch, r.device, offset),
+                    rows=upload_async(torch, r.device, which),
+                    xy=torch.empty(2 * int(n_knots.sum(dtype=np.int64)), dtype=torch.float64, device=r.device))
 
     def _make_spike_list(self, n_pix):
         """the list of the listed spike step (ims_fft_spikes_listed): n_pix / 8 entries (the arms of a bright star's cross are ~3 % of
@@ -501,6 +567,15 @@ class FftDrawer:
         st = r._stream()
         _abi.check(r.lib.ims_fft_kspace_fill(C.byref(P), obj_t.data_ptr(), n, kpre_t.data_ptr(), int(kpre[-1]),
                                              kbuf.data_ptr(), st), "ims_fft_kspace_fill")
+        kn = getattr(state, "knots", None)
+        if kn is not None:
+            # RandomKnots (stamp.fft_knots): filled as points above; their half spectra times the structure factor of their knots
+            _abi.check(r.lib.ims_knot_positions(int(P.seed), obj_t.data_ptr(), n, kn["n_knots"].data_ptr(), kn["sigma"].data_ptr(),
+                                                kn["offset"].data_ptr(), kn["xy"].data_ptr(), st), "ims_knot_positions")
+            _abi.check(r.lib.ims_fft_knots_factor(C.byref(P), obj_t.data_ptr(), kn["rows"].data_ptr(), kn["n_rows"], kn["max_nfft"],
+                                                  kn["n_knots"].data_ptr(), kn["offset"].data_ptr(), kn["xy"].data_ptr(),
+                                                  kbuf.data_ptr(), st), "ims_fft_knots_factor")
+            self.knot_launches = getattr(self, "knot_launches", 0) + 1
         # batched inverse real 2-D FFTs, one batch per FFT size (plain library transform: rocFFT through hipFFT); IMS_FFT_TORCH=1
         # takes torch.fft instead -- the same library behind another front end, kept as the checker
         import os
@@ -551,5 +626,5 @@ class FftDrawer:
         # _last until they are through): the saturated-region boxes too -- freed at the end of this call, their block went back to
         # the allocator and to the next CCD's uploads while k_fft_bbox / k_fft_spikes were still queued (round 5: the rows of the
         # next CCD's k-space fill overwritten, a fault or a hang once the side stream ran behind)
-        self._last = (kbuf, rbuf, final, obj_t, kpre_t, rpre_t, bbox, getattr(self, "_spike_list", None))
+        self._last = (kbuf, rbuf, final, obj_t, kpre_t, rpre_t, bbox, getattr(self, "_spike_list", None), kn)
         return kspace, rbuf

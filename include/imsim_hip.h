@@ -680,6 +680,23 @@ typedef struct ims_fft_params {
 /* elem_prefix[n_objects+1] (device): prefix sum of nfft*(nfft/2+1); kbuf: interleaved (re, im) doubles */
 int  ims_fft_kspace_fill(const ims_fft_params_t* params, const ims_fft_object_t* objects_dev, int64_t n_objects,
                          const int64_t* elem_prefix_dev, int64_t n_elems, double* kbuf, void* stream);
+/* RandomKnots on the FFT branch (base band only: n_alias == 0).  A knots object is n_knots delta functions of equal flux; knot m of
+ * FFT row o sits at d = jac (sigma g0, sigma g1) [arcsec along the pixel axes], (g0, g1) the Gaussian deviate the photon path addresses
+ * by (seed, obj_id, m, knot slot) and jac the FFT row's affine (pixel_scale x winv x the photon row's jac).  Side arrays in the order
+ * of the FFT rows, no struct field: n_knots_dev int32 [n_objects] (0 = not a knots object), sigma_dev double [n_objects] (the photon
+ * row's prof_scale), knot_offset_dev int64 [n_objects] (exclusive prefix sum of n_knots).
+ * ims_knot_positions   : knot_xy_dev[2 (knot_offset[o] + m)] = d, for every row with n_knots > 0.
+ * ims_fft_knots_factor : between ims_fft_kspace_fill (which fills a knots object as a point, prof_ktable IMS_PROF_POINT) and the inverse
+ *                        transform: the half spectrum of every row listed in knot_rows_dev (int32 [n_knot_rows], indices into
+ *                        objects_dev, every one with n_knots > 0) is multiplied in place by the structure factor
+ *                        S(kx_j, ky_i) = (1 / N) sum_m exp(-i (kx_j dx_m + ky_i dy_m)) on ims_fft_kspace_fill's grid.  max_nfft: the largest
+ *                        nfft among the listed rows.  Rows not listed are neither read nor written; n_knot_rows == 0 launches nothing.
+ *                        The sum runs over m ascending with one association: the result does not depend on the launch geometry. */
+int  ims_knot_positions(uint64_t seed, const ims_fft_object_t* objects_dev, int64_t n_objects, const int32_t* n_knots_dev,
+                        const double* sigma_dev, const int64_t* knot_offset_dev, double* knot_xy_dev, void* stream);
+int  ims_fft_knots_factor(const ims_fft_params_t* params, const ims_fft_object_t* objects_dev, const int32_t* knot_rows_dev,
+                          int64_t n_knot_rows, int32_t max_nfft, const int32_t* n_knots_dev, const int64_t* knot_offset_dev,
+                          const double* knot_xy_dev, double* kbuf, void* stream);
 /* Optional spike step between the inverse transform and ims_fft_finish: clip rbuf_in, find each object's
  * saturated bounding box (bbox_dev: int32 [n_objects][4] scratch = rowmin,rowmax,colmin,colmax), write
  * the spiked image to rbuf_out.  No-op copy when params->spikes.enabled == 0. */
