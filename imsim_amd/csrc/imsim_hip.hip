@@ -1405,11 +1405,17 @@ __global__ __launch_bounds__(256) void k_update_distortions(const ims_sensor_t* 
             if (charge == 0.0) continue;
             any = true;
             const double w = ddiv(charge, s.num_elec);
-            const double* dist = s.distortions + ((int64_t)(di + cx) * s.ny + (dj + cy)) * nv * 2;
+            // An edge takes the table entry of the pixel it is the bottom row / left edge of.  On the extra row / column of a qdist
+            // that reaches the stamp's rim (4 with the 9 x 9 files) that pixel is not tabulated: the edge is then the top row /
+            // right edge of the stamp's last pixel, read from its end (top row) or in place (right edge, bottom to top).
+            const bool row_out = dj + cy >= s.ny, col_out = di + cx >= s.nx;
             for (int n = 0; n < npo; ++n) {
                 if (n <= nV + 1 && di == q + 1) continue;
                 if (n > nV + 1 && dj == q + 1) continue;
-                const int vtx = owned_to_vertex(nV, n);
+                const bool bottom = n <= nV + 1;
+                const int ti = di + cx - ((!bottom && col_out) ? 1 : 0), tj = dj + cy - ((bottom && row_out) ? 1 : 0);
+                const int vtx = bottom ? (row_out ? 3 * nV + 3 - n : n) : (col_out ? n : owned_to_vertex(nV, n));
+                const double* dist = s.distortions + ((int64_t)ti * s.ny + tj) * nv * 2;
                 pts[2 * n] = fma(dist[2 * vtx], w, pts[2 * n]);
                 pts[2 * n + 1] = fma(dist[2 * vtx + 1], w, pts[2 * n + 1]);
             }
@@ -3683,6 +3689,8 @@ static int update_distortions_impl(const ims_sensor_t* sensor_dev, const ims_sen
     if (n_slots == 0) return IMS_OK;
     if (!tile_prefix_dev || !changed_dev) return set_err(IMS_ERR_ARG, "tile_prefix/changed is NULL");
     if (sensor_host && sensor_host->qdist > UQMAX) return set_err(IMS_ERR_UNSUPPORTED, "qdist > 4 not supported");
+    if (sensor_host && (sensor_host->qdist < 0 || 2 * sensor_host->qdist + 1 > sensor_host->nx || 2 * sensor_host->qdist + 1 > sensor_host->ny))
+        return set_err(IMS_ERR_UNSUPPORTED, "qdist reaches beyond the tabulated stamp of the sensor model");
     int64_t begin, count;
     int rc = slot_range_cells(sensor_host, first_slot, n_slots, &begin, &count);
     if (rc) return rc;

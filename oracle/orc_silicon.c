@@ -201,13 +201,18 @@ void orc_sensor_update_distortions(const ims_sensor_t* s, int first_slot, int n_
                         double charge = s->bf_delta[cell_index(sl, si, sj)];
                         if (charge == 0.0) continue;
                         double w = charge / s->num_elec;
-                        const double* dist = s->distortions + ((int64_t)(di + cx) * s->ny + (dj + cy)) * nv * 2;
+                        /* beyond the tabulated stamp (the extra row / column of a qdist that reaches its rim) an edge
+                           is the top row / right edge of the stamp's last pixel */
+                        const int row_out = dj + cy >= s->ny, col_out = di + cx >= s->nx;
                         for (int n = 0; n < npo; ++n) {
                             /* the bottom row (shared with the pixel below) takes the extra row but not the
                                extra column; the left edge (shared with the pixel to the left) the reverse */
                             if (n <= nV + 1 && di == q + 1) continue;
                             if (n > nV + 1 && dj == q + 1) continue;
-                            int vtx = owned_to_vertex(s, n);
+                            const int bottom = n <= nV + 1;
+                            const int ti = di + cx - ((!bottom && col_out) ? 1 : 0), tj = dj + cy - ((bottom && row_out) ? 1 : 0);
+                            const double* dist = s->distortions + ((int64_t)ti * s->ny + tj) * nv * 2;
+                            int vtx = bottom ? (row_out ? 3 * nV + 3 - n : n) : (col_out ? n : owned_to_vertex(s, n));
                             pts[2 * n] = orc_fma(dist[2 * vtx], w, pts[2 * n]);
                             pts[2 * n + 1] = orc_fma(dist[2 * vtx + 1], w, pts[2 * n + 1]);
                         }
