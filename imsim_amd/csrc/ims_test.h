@@ -4,7 +4,8 @@
 // Entry points: ims_test_math, ims_test_optical_screen.
 #pragma once
 
-// device math probe for the parity tests (which: 0 log,1 exp,2 sincos2pi,3 atan,4 sincos,5 tanh,6 gauss,7 dsqrt_n,8 ddiv of pairs,9 dsqrt0)
+// device math probe for the parity tests (which: 0 log,1 exp,2 sincos2pi,3 atan,4 sincos,5 tanh,6 gauss,7 dsqrt_n,8 ddiv of pairs,9 dsqrt0,
+// 10 sincos2pi of a word,11 log of a word,12 gauss_word_cos of pairs,13 dlgamma)
 __global__ void k_test_math(int which, const double* __restrict__ in, double* __restrict__ out, int64_t n,
                             uint64_t seed, int64_t obj, uint32_t slot)
 {
@@ -27,6 +28,8 @@ __global__ void k_test_math(int which, const double* __restrict__ in, double* __
     case 10: sincos2pi_w((uint32_t)in[i], s, c); out[2 * i] = s; out[2 * i + 1] = c; break;
     case 11: out[i] = dlog_w((uint32_t)in[i]); break;
     case 12: out[i] = gauss_word_cos((uint32_t)in[2 * i], (uint32_t)in[2 * i + 1]); break;
+    // log Gamma of the Poisson deviate's acceptance test (x > 0)
+    case 13: out[i] = dlgamma(in[i]); break;
     }
 }
 

@@ -124,6 +124,10 @@ class LSST_ImageBuilderBase:
         pixel_areas: device tensor [ny][nx] from sky_pixel_areas (a Silicon sensor's pixels collect sky in proportion to
         their area), folded into the multiplier."""
         from . import _abi
+        from .readout import DARK_STREAM
+        if NOISE_STREAM + int(stream_id) == DARK_STREAM:
+            # with the CCD's seed the sky noise would draw from the uniforms of its dark current
+            raise ValueError(f"stream_id {int(stream_id)} addresses the dark-current stream of the readout")
         torch = renderer.torch
         sc = renderer.scene
         base_t = None

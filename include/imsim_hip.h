@@ -1198,7 +1198,8 @@ int  ims_last_kernel_ms(float* ms, int* n_launches);
 int  ims_enable_timing(int which);
 
 /* ---- numerics probe used by the parity tests: evaluates the spec's elementary functions on device ----
- * which: 0 log, 1 exp, 2 sincos2pi (2 outputs), 3 atan, 4 sincos (2), 5 tanh, 6 gaussian pair of draw(seed,obj,i,slot) (2) */
+ * which: 0 log, 1 exp, 2 sincos2pi (2 outputs), 3 atan, 4 sincos (2), 5 tanh, 6 gaussian pair of draw(seed,obj,i,slot) (2),
+ * 13 log Gamma as the Poisson deviate evaluates it (x > 0) */
 /* sizeof() of the ABI structs as compiled, for binding self-checks:
  * 0 object, 1 radial_tables, 2 lin_tables, 3 psf_component, 4 op, 5 surface, 6 tansip, 7 optics, 8 bf_slot,
  * 9 sensor, 10 photons, 11 render_params, 12 plan_item, 13 atmosphere, 14 fft_object, 15 fft_params, 16 readout,

@@ -77,7 +77,8 @@ void orc_fft_kspace_fill(const ims_fft_params_t* P, const ims_fft_object_t* objs
     }
 }
 
-static double orc_lgamma(double x)
+/* log Gamma(x) for x > 0: upward recurrence to x >= 8, then the Stirling series (orc_test_math 13 probes it) */
+double orc_lgamma(double x)
 {
     double shift = 0.0;
     while (x < 8.0) { shift = shift + orc_log(x); x = x + 1.0; }

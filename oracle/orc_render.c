@@ -72,6 +72,7 @@ int orc_shoot_pool(const ims_render_params_t* P, const int64_t* photon_offset, i
 }
 
 /* test hooks for the elementary functions */
+double orc_lgamma(double x);
 void orc_test_math(int which, const double* in, double* out, int64_t n)
 {
     for (int64_t i = 0; i < n; ++i) {
@@ -85,6 +86,7 @@ void orc_test_math(int which, const double* in, double* out, int64_t n)
         case 10: { double s, c; orc_sincos2pi_w((uint32_t)in[i], &s, &c); out[2 * i] = s; out[2 * i + 1] = c; break; }
         case 11: out[i] = orc_log_w((uint32_t)in[i]); break;
         case 12: out[i] = orc_gauss_word_cos((uint32_t)in[2 * i], (uint32_t)in[2 * i + 1]); break;
+        case 13: out[i] = orc_lgamma(in[i]); break;
         }
     }
 }

@@ -42,6 +42,25 @@ def test_elementary_functions_accuracy():
     np.testing.assert_allclose(orc_loader.math_probe(5, x), np.tanh(x), atol=1e-15)
 
 
+def test_log_is_good_to_an_ulp():
+    """|log - ln x| <= 2^-53 |ln x| + 2^-51 for normal x > 0, from the spec's evaluation (u = 2^-53): x = 2^e m with m in
+    (0.707, 1.415); s = (m - 1) / (m + 1), |s| <= 0.1716, carries two roundings (m - 1 is exact); the series p in [1, 1.01]
+    is good to 1.2 u (its last fma, z = s^2 at 5 u times p's slope 1/3, the rounded 1/3); truncated after z^12 / 25, which
+    leaves 2 s z^13 / 27 < 1e-21; lm = 2 s p adds one rounding: 4.2 u relative of at most 0.3466 = 1.46 u.  e LN2_HI is exact
+    (LN2_HI has 32 trailing zero bits), the inner fma rounds a number below 0.347 (0.35 u), the outer one the result
+    (u |ln x|).  Together u |ln x| + 1.81 u; asserted with 4 u = 2^-51 for the constant.  The Poisson deviate's near-tie
+    bound (tests/noise_deviate_ref.py) is built on this: k log(mean) at mean 1e9 multiplies it by 1e9."""
+    rng = np.random.default_rng(5)
+    x = np.concatenate([10 ** rng.uniform(-300, 300, 200000), rng.uniform(0.5, 2.0, 200000), 10 ** rng.uniform(0, 10, 200000),
+                        [1.0, 2.0, 0.5, np.nextafter(1.0, 0), np.nextafter(1.0, 2), 1.4142135623730951,
+                         np.nextafter(1.4142135623730951, 2), 1e9, 2.0 ** -53, 2.2250738585072014e-308]])
+    want = np.log(x.astype(np.longdouble))
+    err = np.abs(orc_loader.math_probe(0, x).astype(np.longdouble) - want)
+    bound = 2.0 ** -53 * np.abs(want) + 2.0 ** -51
+    print(f"log: worst error / bound {float((err / bound).max()):.3f}")
+    assert np.all(err <= bound)
+
+
 def test_gaussian_deviates_are_standard_normal():
     g = orc_loader.gauss_probe(seed=7, obj=3, n=500000, slot=2)
     assert abs(g.mean()) < 5e-3
