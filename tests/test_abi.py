@@ -183,7 +183,15 @@ def test_argument_errors_are_reported_before_any_launch():
     op.kind = _abi.IMS_OP_PHOTON_DCR
     op.p[0], op.p[1], op.p[2], op.p[3] = 620.0, 69.328, 293.15, 1.067
     assert lib.ims_fill_derived_op(C.byref(op)) == 0
-    assert 1.0e-7 < op.p[5] < 1.0e-5 and 0.0 < op.p[6] < 1.0e-5 and 1.0e-4 < op.p[7] < 4.0e-4      # n - 1 ~ 1.9e-4 at 69 kPa
+    # the air factors and the refraction constant at the base wavelength: equal to the independent restatement of Filippenko /
+    # Edlen (tests/photon_ops_ref.py) within its derived bound of 16 roundings, for the site and two other atmospheres
+    import photon_ops_ref
+    for atm in ((69.328, 293.15, 1.067), (101.325, 288.15, 0.0), (85.0, 258.15, 0.19)):
+        op.p[0], (op.p[1], op.p[2], op.p[3]) = 620.0, atm
+        assert lib.ims_fill_derived_op(C.byref(op)) == 0
+        for k, (want, bound) in zip((5, 6, 7), photon_ops_ref.dcr_derived([op.p[m] for m in range(4)])):
+            assert abs(photon_ops_ref.LD(op.p[k]) - want) <= bound, (atm, k, op.p[k], float(want))
+    assert 1.0e-4 < op.p[7] < 4.0e-4
 
 
 def test_derived_constants_are_the_plain_ieee_expressions():
