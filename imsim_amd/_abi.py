@@ -345,7 +345,8 @@ EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_
            "ims_fft_inverse", "ims_fft_inverse_raw", "ims_fft_spikes_listed", "ims_fft_warm", "ims_comm_unique_id", "ims_comm_init", "ims_comm_destroy", "ims_reduce_image", "ims_allreduce_delta",
            "ims_count_inexact", "ims_struct_size", "ims_test_math", "ims_opd", "ims_opd_perturbed",
            "ims_paint_cosmic_rays", "ims_test_optical_screen", "ims_trace_field_points", "ims_trace_field_points_perturbed",
-           "ims_object_spectra", "ims_psf_moments", "ims_knot_positions", "ims_fft_knots_factor"]
+           "ims_object_spectra", "ims_psf_moments", "ims_knot_positions", "ims_fft_knots_factor",
+           "ims_fft_image_factor"]
 
 _LIB_PATH = tuning.env("IMSIM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libimsim_hip.so")
 _lib = None
@@ -412,6 +413,7 @@ def load():
     lib.ims_fft_finish.argtypes = [C.POINTER(FftParams), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]
     lib.ims_knot_positions.argtypes = [C.c_uint64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.ims_fft_knots_factor.argtypes = [C.POINTER(FftParams), c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]
+    lib.ims_fft_image_factor.argtypes = [C.POINTER(FftParams), c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]
     lib.ims_fft_spikes.argtypes = [C.POINTER(FftParams), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]
     lib.ims_fft_spike_table.argtypes = [C.POINTER(Spikes), c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.ims_run_plan.argtypes = [C.POINTER(PlanItem), c_i64, c_vp, C.POINTER(Sensor), c_vp, C.POINTER(c_vp), c_i32]

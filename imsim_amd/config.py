@@ -472,6 +472,17 @@ def parse_fft_knots(stamp_cfg, ev):
     return bool(v)
 
 
+def parse_fft_stamps(stamp_cfg, ev):
+    """stamp.fft_stamps (an extension of ours, default false): FITS-stamp objects (galsim.InterpolatedImage) above stamp.fft_sb_thresh
+    take the FFT branch, as the reference's do (imsim/stamp.py:270-308), instead of staying photon-shot at any flux.  Off by default:
+    switched on, the images and truth records of catalogs with bright stamps change (another branch draws them).  Anything but a
+    boolean is a config error."""
+    v = ev.value(stamp_cfg.get("fft_stamps", False))
+    if not isinstance(v, (bool, np.bool_)):
+        raise GalSimConfigError(f"stamp.fft_stamps must be true or false, got {v!r}")
+    return bool(v)
+
+
 def parse_atm_psf_options(atm_cfg, stamp_cfg, ev, data_dir, res, itype="LSST_Image", psf_cfg=None):
     """What input.atm_psf's doOpt and save_file ask for, checked before any GPU work.  doOpt (the optical phase screen,
     atm_psf.AtmosphericPSF) needs the three tables of <data_dir>/optics_data/, room for one more PSF component and a render in
@@ -860,6 +871,7 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     crs = parse_cosmic_rays(out, ev, data_dir)
     parse_atm_psf_options(inp.get("atm_psf"), stamp_cfg, ev, data_dir, res, itype, cfg.get("psf"))
     fft_knots = parse_fft_knots(stamp_cfg, ev)
+    fft_stamps = parse_fft_stamps(stamp_cfg, ev)
     tel_cfg = inp.get("telescope", {})
     build_telescope(tel_cfg, ev, band)                                  # ... the telescope's among them
     wcs_cfg = parse_image_wcs(image, res)
@@ -1043,13 +1055,13 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
             ctx.pooling = dict(cat=cat, phot_flux=phot, make_objects=make_objects, max_flux_simple=max_simple, seed=seed_ccd, truth=truth,
                                fft_sb_thresh=float(ev.value(stamp_cfg.get("fft_sb_thresh", 0.0))), kpsf=kpsf, fwhm_total=fwhm_total,
                                diffraction_fft=dfft, wavelength=wl_eff, extra_ktables=extra_ktables, vignetting=vig, checkpoint=chk,
-                               fft_knots=fft_knots)
+                               fft_knots=fft_knots, fft_stamps=fft_stamps)
         else:
             ctx.job = builder.prepare(scene, cat, phot, make_objects,
                                       fft_sb_thresh=float(ev.value(stamp_cfg.get("fft_sb_thresh", 0.0))), max_flux_simple=max_simple,
                                       draw_method=ev.value(stamp_cfg.get("draw_method", "auto")), kpsf=kpsf, fwhm_total=fwhm_total,
                                       diffraction_fft=dfft, wavelength=wl_eff, nrecalc=nrecalc, extra_ktables=extra_ktables,
-                                      vignetting=vig, fft_knots=fft_knots)
+                                      vignetting=vig, fft_knots=fft_knots, fft_stamps=fft_stamps)
             ctx.job.want_realized = True
         # sky + noise (imsim/lsst_image.py:128-200) when a numeric sky level is configured; the Rubin sky model,
         # vignetting and fringing inputs are out of scope and reported as ignored

@@ -5182,5 +5182,6 @@ int ims_trace_field_points_perturbed(const ims_optics_perturbed_t* optics_dev, c
 }  // extern "C"
 
 #include "ims_knots.h"          // RandomKnots on the FFT branch: knot positions and the structure-factor pass
+#include "ims_stamp_fft.h"      // FITS stamps on the FFT branch: the pixel spectrum times the interpolant's transform
 #include "ims_exchange.h"       // RCCL exchanges between the GPUs of a node
 #include "ims_test.h"           // device probes of the parity tests

@@ -940,7 +940,10 @@ def _focal_streams(torch, device, peek=False, top_index=None):
 _PINNED_ARENAS = []            # (page-locked tensor, events after the last run that copies out of it)
 
 
-_PINNED_LOCK = threading.Lock()
+# Re-entrant: _pinned_arena queries events under the lock, a garbage collection that starts there can run NativePlan.__del__ on the
+# same thread, and that takes the lock to hand its arena back (with a plain Lock the thread waited for itself for ever).  What a
+# nested holder does is append to the list, which neither the scan of _pinned_arena nor its pop of an earlier index minds.
+_PINNED_LOCK = threading.RLock()
 
 
 def _pinned_arena(torch, nbytes):

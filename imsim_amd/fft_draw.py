@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _abi, tables, tuning
 from ._abi import FFT_OBJECT_DTYPE, FftParams, KPsf
-from .catalog import KIND_KNOTS, KIND_STREAK
+from .catalog import KIND_IMAGE, KIND_KNOTS, KIND_STREAK
 
 KOLMOGOROV_K0 = 2.992934 * 0.9758634299       # k0 * fwhm for exp(-(k/k0)^(5/3))  [rad/arcsec * arcsec]
 
@@ -104,7 +104,7 @@ def kpsf_peak_per_flux(kpsf, ktables=None, q_step=None, n_base=2):
 
 
 def max_surface_brightness(flux, kind, hlr, fwhm_total=None, pixel_scale=0.2, sersic_n=None, jac_det=None, psf_peaks=None,
-                           box_area=None, fft_knots=False):
+                           box_area=None, fft_knots=False, fft_stamps=False, image_peaks=None):
     """`Convolve(gal_achrom, fft_psf).withFlux(F).max_sb / 2 * pixel_scale^2` [photons/pixel], the quantity
     get_fft_psf_maybe compares with fft_sb_thresh (imsim/psf_utils.py:201-212).  GalSim's max_sb of a convolution is the
     estimate that is exact for Gaussians: F / sum_i (1 / peak_i) with peak_i the central surface brightness per unit
@@ -114,7 +114,12 @@ def max_surface_brightness(flux, kind, hlr, fwhm_total=None, pixel_scale=0.2, se
     fft_knots (stamp.fft_knots, off by default): RandomKnots counts as GalSim counts it -- a sum of DeltaFunctions, each of which adds
     nothing to the convolution's estimate (galsim/convolve.py, Convolution.max_sb: the sum of flux / max_sb over the components, to
     which a delta function adds 0), so the estimate is the PSF's alone, as for a point source.  (Stated from GalSim's source: GalSim is
-    not installed where this was written, so no call confirms it.)  Off: knots get no estimate and stay photon-shot."""
+    not installed where this was written, so no call confirms it.)  Off: knots get no estimate and stay photon-shot.
+    fft_stamps (stamp.fft_stamps, off by default): a FITS-stamp object (galsim.InterpolatedImage) counts with the peak of its pixels,
+    per unit flux max(w_m) / (p^2 |det J|): w_m its non-negative pixels normalised to sum 1, p the stamp's pixel scale, J the object's
+    affine (jac_det).  image_peaks: max(w_m) / p^2 per object [1 / arcsec^2] (image_peaks_per_flux; read only where kind is
+    KIND_IMAGE).  (Stated from GalSim's source as the value of InterpolatedImage.max_sb -- the largest pixel over the pixel's area:
+    GalSim is not installed where this was written, so no call confirms it.)  Off, or without image_peaks: no estimate, photon-shot."""
     from scipy import special
     flux = np.asarray(flux, dtype=np.float64)
     kind = np.asarray(kind)
@@ -138,14 +143,21 @@ def max_surface_brightness(flux, kind, hlr, fwhm_total=None, pixel_scale=0.2, se
     box = (kind == KIND_STREAK) if box_area is not None else np.zeros(kind.shape, dtype=bool)
     if box.any():
         inv[box] = inv[box] + np.broadcast_to(np.asarray(box_area, dtype=np.float64), kind.shape)[box]
-    other = (~gal) & (~box) & (kind != 0)   # knots and FITS images have no k-space form here: a broad stand-in keeps them photon-shot
+    img = (kind == KIND_IMAGE) if (fft_stamps and image_peaks is not None) else np.zeros(kind.shape, dtype=bool)
+    if img.any():
+        peak = np.broadcast_to(np.asarray(image_peaks, dtype=np.float64), kind.shape)[img]
+        if jac_det is not None:
+            peak = peak / np.abs(np.broadcast_to(np.asarray(jac_det, dtype=np.float64), kind.shape)[img])
+        with np.errstate(divide="ignore"):
+            inv[img] = inv[img] + 1.0 / peak
+    other = (~gal) & (~box) & (~img) & (kind != 0)   # knots and FITS images get no estimate by default: a broad stand-in keeps them photon-shot
     if fft_knots:
         other &= kind != KIND_KNOTS         # (knots behind stamp.fft_knots: the PSF's estimate alone, as for kind 0)
     inv[other] = np.inf
     return flux / inv / 2.0 * pixel_scale ** 2
 
 
-def has_kspace_form(kind, objects=None, pixel_scale=0.2, fft_knots=False, n_alias=0):
+def has_kspace_form(kind, objects=None, pixel_scale=0.2, fft_knots=False, n_alias=0, fft_stamps=False, image_sizes=None):
     """Which objects the FFT branch can draw at all: points, Sersic profiles and streaks (galsim.Box).  RandomKnots and FITS-image
     objects have no k-space form here and stay photon-shot whatever their flux.  So does a streak that does not fit the periodic
     grid its stamp gives it (objects: the OBJECT_DTYPE rows, same length as kind) -- a good stamp size capped at catalog.NMAX, or a
@@ -154,31 +166,53 @@ def has_kspace_form(kind, objects=None, pixel_scale=0.2, fft_knots=False, n_alia
     |J| (length, width) with J = s winv R(pa), against nfft * pixel_scale.
     fft_knots (stamp.fft_knots, off by default): RandomKnots has a k-space form too -- the point's spectrum times the structure factor
     of its knots (ims_fft_knots_factor) -- but only in the base band: with n_alias > 0 (alias_order of the FFT-mode PSF) the structure
-    factor is no common factor of the folded sum, and knots stay photon-shot."""
+    factor is no common factor of the folded sum, and knots stay photon-shot.
+    fft_stamps (stamp.fft_stamps, off by default): so has a FITS-stamp object -- the point's spectrum times the spectrum of its pixel
+    lattice and the transform of the interpolant (ims_fft_image_factor) -- under the same condition on n_alias, and only if the stamp
+    fits the periodic grid its stamp size gives it: the streak's test over the stamp's bounding box plus the interpolant's support of
+    3 stamp pixels on every side, |J| (p (w + 6), p (h + 6)).  image_sizes: (w, h) of every image profile of the scene, indexed by the
+    rows' prof_aux; needed whenever `objects` holds a stamp object and the switch is on.  A stamp that does not fit stays with the
+    photons."""
     kind = np.asarray(kind)
     box = kind == KIND_STREAK
     ok = (kind < 3) | box
     if fft_knots and n_alias <= 0:
         ok = ok | (kind == KIND_KNOTS)
+    img = kind == KIND_IMAGE
+    if fft_stamps and n_alias <= 0 and img.any():
+        ok = ok | img
+        if objects is not None:
+            if image_sizes is None:
+                raise ValueError("has_kspace_form: fft_stamps with object rows needs image_sizes")
+            o = objects[img]
+            wh = np.asarray(image_sizes, dtype=np.float64).reshape(-1, 2)[o["prof_aux"].astype(np.int64)]
+            ok[img] = _fits_grid(o, (wh[:, 0] + 6.0) * o["prof_scale"], (wh[:, 1] + 6.0) * o["prof_scale"], pixel_scale)
     if objects is not None and box.any():
         o = objects[box]
-        size = o["stamp_xmax"] - o["stamp_xmin"] + 1                    # the grid build_fft_objects will take
-        grid = np.array([next_fft_size(int(n)) for n in size], dtype=np.float64) * pixel_scale
-        w, j = o["winv"] * pixel_scale, o["jac"]
-        L, W = o["prof_scale"], o["prof_aux"]
-        ex = np.abs(w[:, 0] * j[:, 0] + w[:, 1] * j[:, 2]) * L + np.abs(w[:, 0] * j[:, 1] + w[:, 1] * j[:, 3]) * W
-        ey = np.abs(w[:, 2] * j[:, 0] + w[:, 3] * j[:, 2]) * L + np.abs(w[:, 2] * j[:, 1] + w[:, 3] * j[:, 3]) * W
-        ok[box] = np.maximum(ex, ey) <= grid
+        ok[box] = _fits_grid(o, o["prof_scale"], o["prof_aux"], pixel_scale)
     return ok
 
 
-def use_fft(nominal_flux, kind, hlr, fwhm_total, fft_sb_thresh, fft_knots=False, **kw):
-    """The FFT-vs-phot decision of LSST_SiliconBuilder.buildPSF (stamp.py:275-308).  fft_knots: see max_surface_brightness."""
+def _fits_grid(o, L, W, pixel_scale):
+    """whether the box of sides (L, W) [arcsec] along the profile axes of the OBJECT_DTYPE rows `o` fits, along both pixel axes, the
+    periodic grid build_fft_objects will give every row"""
+    size = o["stamp_xmax"] - o["stamp_xmin"] + 1                        # the grid build_fft_objects will take
+    grid = np.array([next_fft_size(int(n)) for n in size], dtype=np.float64) * pixel_scale
+    w, j = o["winv"] * pixel_scale, o["jac"]
+    ex = np.abs(w[:, 0] * j[:, 0] + w[:, 1] * j[:, 2]) * L + np.abs(w[:, 0] * j[:, 1] + w[:, 1] * j[:, 3]) * W
+    ey = np.abs(w[:, 2] * j[:, 0] + w[:, 3] * j[:, 2]) * L + np.abs(w[:, 2] * j[:, 1] + w[:, 3] * j[:, 3]) * W
+    return np.maximum(ex, ey) <= grid
+
+
+def use_fft(nominal_flux, kind, hlr, fwhm_total, fft_sb_thresh, fft_knots=False, fft_stamps=False, **kw):
+    """The FFT-vs-phot decision of LSST_SiliconBuilder.buildPSF (stamp.py:275-308).  fft_knots, fft_stamps (with image_peaks among
+    the keywords): see max_surface_brightness."""
     nominal_flux = np.asarray(nominal_flux, dtype=np.float64)
     if not fft_sb_thresh:
         return np.zeros(nominal_flux.shape, dtype=bool)
     cand = (nominal_flux >= 1.0e6) & (nominal_flux >= fft_sb_thresh)
-    return cand & (max_surface_brightness(nominal_flux, kind, hlr, fwhm_total, fft_knots=fft_knots, **kw) > fft_sb_thresh)
+    return cand & (max_surface_brightness(nominal_flux, kind, hlr, fwhm_total, fft_knots=fft_knots, fft_stamps=fft_stamps,
+                                                 **kw) > fft_sb_thresh)
 
 
 def profile_ktable_ids(scene, prof_table, n_extra_ktables=0, n_base=2):
@@ -239,6 +273,47 @@ def knot_side_arrays(objects, order):
     return n_knots, sigma, offset
 
 
+def image_pixel_lists(images):
+    """The image profiles of a scene (Scene.image_profiles: 2-D arrays [h][w]) as ims_fft_image_factor reads them: (image_size int32
+    [n][2] = (w, h); image_offset int64 [n + 1], the prefix sum of the number of positive pixels; pixel_ab int32 [total][2], column a
+    and row b of every positive pixel in row-major order; pixel_w float64 [total], the pixel over the sum of the image's positive
+    pixels).  Negative and zero pixels are left out: engine.image_profile_cdf gives them no photon either."""
+    size, offset, ab, w = [], [0], [], []
+    for img in images:
+        v = np.clip(np.asarray(img, dtype=np.float64), 0.0, None)
+        if v.ndim != 2:
+            raise ValueError("image profile: a 2-D array")
+        tot = v.sum()
+        if not tot > 0.0:
+            raise ValueError("image profile has no positive pixel")
+        b, a = np.nonzero(v > 0.0)                                       # (row-major: b ascending, a ascending within a row)
+        size.append((v.shape[1], v.shape[0]))
+        ab.append(np.stack([a, b], axis=1))
+        w.append(v[b, a] / tot)
+        offset.append(offset[-1] + len(a))
+    return (np.asarray(size, dtype=np.int32).reshape(-1, 2), np.asarray(offset, dtype=np.int64),
+            np.ascontiguousarray(np.concatenate(ab) if ab else np.zeros((0, 2)), dtype=np.int32),
+            np.ascontiguousarray(np.concatenate(w) if w else np.zeros(0), dtype=np.float64))
+
+
+def image_peaks_per_flux(images, image_index, image_scale):
+    """max(w_m) / p^2 [1 / arcsec^2] for every object of a catalog (max_surface_brightness's image_peaks): image_index, image_scale as
+    instcat leaves them in the catalog dict; 0 where the scale is 0 (no stamp object)."""
+    top = np.array([float(np.clip(im, 0.0, None).max() / np.clip(im, 0.0, None).sum()) for im in images] or [0.0])
+    idx = np.clip(np.asarray(image_index, dtype=np.int64), 0, len(top) - 1)
+    p = np.asarray(image_scale, dtype=np.float64)
+    return np.where(p > 0.0, top[idx] / np.where(p > 0.0, p * p, 1.0), 0.0)
+
+
+def image_side_arrays(objects, order):
+    """The per-row side array of ims_fft_image_factor for the OBJECT_DTYPE rows that build_fft_objects turned into FFT rows, in the
+    order of those rows (`order`: build_fft_objects's second result): row_image (int32), the index of the row's image profile
+    (the photon row's prof_aux) or -1 for everything that is not a FITS-stamp object.  The pixel lists of the profiles themselves
+    (image_pixel_lists) belong to the scene and are uploaded once per renderer.  No struct gains a field."""
+    o = np.asarray(objects)[np.asarray(order)]
+    return np.where(o["prof_table"] == _abi.IMS_PROF_IMAGE, o["prof_aux"], -1.0).astype(np.int32)
+
+
 def kpsf_alias_order(kpsf, extra_ktables=(), n_base=2, pixel_scale=0.2):
     """alias_order of a k-space PSF as FftDrawer will find it (ims_fft_params_t.n_alias), from the PSF's own k-tables alone: the
     profile tables in front of them (n_base) are not looked at by a PSF component."""
@@ -250,9 +325,10 @@ def kpsf_alias_order(kpsf, extra_ktables=(), n_base=2, pixel_scale=0.2):
 
 
 class DrawState(tuple):
-    """what FftDrawer._upload hands to _run: (rows, obj_t, nfft, kpre, rpre, kpre_t, rpre_t, kbuf, rbuf), and in `knots` the device
-    side of a batch's RandomKnots objects (None: the batch has none)"""
+    """what FftDrawer._upload hands to _run: (rows, obj_t, nfft, kpre, rpre, kpre_t, rpre_t, kbuf, rbuf), in `knots` the device
+    side of a batch's RandomKnots objects and in `images` that of its FITS-stamp objects (None: the batch has none)"""
     knots = None
+    images = None
 
 
 def set_spikes(P, diffraction_fft, wavelength, renderer=None):
@@ -433,19 +509,21 @@ class FftDrawer:
                                         renderer.scene.seed, add_noise, lambda a: renderer.mem.put(a, np.float64))
         self.P.image = renderer.image.data_ptr()
         self.knot_launches = 0                  # draws that ran the structure-factor pass (a batch without RandomKnots launches nothing)
+        self.image_launches = 0                 # draws that ran the stamp pass (ims_fft_image_factor; no stamp row, no launch)
         set_spikes(self.P, diffraction_fft, wavelength, renderer)
 
-    def draw(self, fft_objects, realized=None, knots=None):
+    def draw(self, fft_objects, realized=None, knots=None, images=None):
         """fft_objects: FFT_OBJECT_DTYPE rows sorted by nfft (build_fft_objects).  `realized`:
-        optional float64 device tensor [n].  knots: knot_side_arrays of the rows (stamp.fft_knots), None without RandomKnots objects."""
+        optional float64 device tensor [n].  knots: knot_side_arrays of the rows (stamp.fft_knots), None without RandomKnots objects.
+        images: image_side_arrays of the rows (stamp.fft_stamps), None without FITS-stamp objects."""
         if len(fft_objects) == 0:
             return
-        return self._run(self._upload(fft_objects, knots), realized)
+        return self._run(self._upload(fft_objects, knots, images), realized)
 
-    def prepared(self, fft_objects, knots=None):
+    def prepared(self, fft_objects, knots=None, images=None):
         """Upload the rows and allocate the k-space / real-space buffers once; returns a zero-argument callable that
         draws the batch (bench.py: the timed region starts with its inputs resident in HBM)."""
-        state = self._upload(fft_objects, knots)
+        state = self._upload(fft_objects, knots, images)
 
         def launch():
             self._run(state, None)
@@ -455,11 +533,12 @@ class FftDrawer:
         launch.kspace_elements = int(np.sum(nfft * (nfft // 2 + 1)))
         return launch
 
-    def prepared_chunked(self, fft_objects, max_pixels=1 << 30):
+    def prepared_chunked(self, fft_objects, max_pixels=1 << 30, images=None):
         """`prepared` for a table whose buffers do not fit at once (thousands of bright stars on 1024^2 .. 4096^2 grids: 24 B per grid
         point): the rows -- grouped by FFT size, as build_fft_objects leaves them -- are cut into consecutive chunks of at most
         max_pixels grid points that share ONE set of k-space / real-space / spike buffers and are drawn one after the other on the
-        current stream.  Same launches per chunk as `prepared`; returns a zero-argument callable."""
+        current stream.  Same launches per chunk as `prepared`; returns a zero-argument callable.  images: image_side_arrays of the
+        rows; every chunk carries the part of its own rows."""
         torch, r = self.torch, self.r
         rows = np.ascontiguousarray(fft_objects, dtype=FFT_OBJECT_DTYPE)
         nfft = rows["nfft"].astype(np.int64)
@@ -489,8 +568,11 @@ class FftDrawer:
             rpre = np.concatenate([[0], np.cumsum(nf * nf)]).astype(np.int64)
             part["k_offset"], part["r_offset"] = kpre[:-1], rpre[:-1]
             obj_t = upload_async(torch, r.device, part.view(np.uint8).reshape(-1))
-            states.append((part, obj_t, nf, kpre, rpre, upload_async(torch, r.device, kpre), upload_async(torch, r.device, rpre),
-                           kbuf[:int(kpre[-1])], rbuf[:int(rpre[-1])]))
+            state = DrawState((part, obj_t, nf, kpre, rpre, upload_async(torch, r.device, kpre), upload_async(torch, r.device, rpre),
+                               kbuf[:int(kpre[-1])], rbuf[:int(rpre[-1])]))
+            if images is not None and np.any(np.asarray(images[a:b]) >= 0):
+                state.images = self._upload_images(part, np.asarray(images)[a:b])
+            states.append(state)
 
         def launch():
             for st in states:
@@ -504,7 +586,7 @@ class FftDrawer:
         launch.keep = (states, kbuf, rbuf, spike)
         return launch
 
-    def _upload(self, fft_objects, knots=None):
+    def _upload(self, fft_objects, knots=None, images=None):
         torch, r = self.torch, self.r
         rows = np.ascontiguousarray(fft_objects, dtype=FFT_OBJECT_DTYPE)
         from .engine import upload_async
@@ -523,7 +605,42 @@ class FftDrawer:
         state = DrawState((rows, obj_t, nfft, kpre, rpre, kpre_t, rpre_t, kbuf, rbuf))
         if knots is not None and np.any(np.asarray(knots[0]) > 0):
             state.knots = self._upload_knots(rows, knots)
+        if images is not None and np.any(np.asarray(images) >= 0):
+            state.images = self._upload_images(rows, images)
         return state
+
+    def _upload_images(self, rows, images):
+        """the side arrays of a batch's FITS-stamp objects on the device: the image of every row, the list of the rows that have one,
+        and the scene's pixel lists (uploaded once per renderer, kept with it)"""
+        torch, r = self.torch, self.r
+        from .engine import upload_async
+        if self.P.n_alias > 0:
+            raise ValueError("FITS stamps on the FFT branch need a PSF without aliases to fold (n_alias == 0): fft_draw.has_kspace_form "
+                             "keeps such objects photon-shot")
+        row_image = np.ascontiguousarray(images, dtype=np.int32)
+        if len(row_image) != len(rows):
+            raise ValueError("images: one entry per FFT row")
+        lists = getattr(r, "_stamp_lists", None)
+        if lists is None:
+            profiles = getattr(r.scene, "image_profiles", None)
+            if not profiles:
+                raise ValueError("images: the scene has no image profiles")
+            interp = {"nearest": 0, "quintic": 1}.get(r.scene.image_interpolant)
+            if interp is None:
+                raise ValueError(f"image_interpolant {r.scene.image_interpolant!r}: 'quintic' or 'nearest'")
+            size, offset, ab, w = image_pixel_lists(profiles)
+            lists = r._stamp_lists = dict(n=len(size), interp=interp, size=upload_async(torch, r.device, size.reshape(-1)),
+                                          offset=upload_async(torch, r.device, offset), ab=upload_async(torch, r.device, ab.reshape(-1)),
+                                          w=upload_async(torch, r.device, w))
+        which = np.flatnonzero(row_image >= 0).astype(np.int32)
+        if (row_image[which] >= lists["n"]).any() or (row_image < -1).any():
+            raise ValueError("images: an image index outside the scene's image profiles")
+        if (rows["prof_ktable"][which] != _abi.IMS_PROF_POINT).any():
+            raise ValueError("images: a FITS-stamp row is filled as a point (prof_ktable -1)")
+        if not (rows["prof_scale"][which] > 0.0).all():
+            raise ValueError("images: a FITS-stamp row carries the stamp's pixel scale in prof_scale")
+        return dict(n_rows=len(which), max_nfft=int(rows["nfft"][which].max()), lists=lists,
+                    row_image=upload_async(torch, r.device, row_image), rows=upload_async(torch, r.device, which))
 
     def _upload_knots(self, rows, knots):
         """the side arrays of a batch's RandomKnots objects on the device, the list of their rows and the buffer of the knots'
@@ -576,6 +693,15 @@ class FftDrawer:
                                                   kn["n_knots"].data_ptr(), kn["offset"].data_ptr(), kn["xy"].data_ptr(),
                                                   kbuf.data_ptr(), st), "ims_fft_knots_factor")
             self.knot_launches = getattr(self, "knot_launches", 0) + 1
+        im = getattr(state, "images", None)
+        if im is not None:
+            # FITS stamps (stamp.fft_stamps): filled as points above; their half spectra times the spectrum of their pixels
+            L = im["lists"]
+            _abi.check(r.lib.ims_fft_image_factor(C.byref(P), obj_t.data_ptr(), im["rows"].data_ptr(), im["n_rows"], im["max_nfft"],
+                                                  im["row_image"].data_ptr(), L["n"], L["size"].data_ptr(), L["offset"].data_ptr(),
+                                                  L["ab"].data_ptr(), L["w"].data_ptr(), L["interp"], kbuf.data_ptr(), st),
+                       "ims_fft_image_factor")
+            self.image_launches = getattr(self, "image_launches", 0) + 1
         # batched inverse real 2-D FFTs, one batch per FFT size (plain library transform: rocFFT through hipFFT); IMS_FFT_TORCH=1
         # takes torch.fft instead -- the same library behind another front end, kept as the checker
         import os
@@ -626,5 +752,5 @@ class FftDrawer:
         # _last until they are through): the saturated-region boxes too -- freed at the end of this call, their block went back to
         # the allocator and to the next CCD's uploads while k_fft_bbox / k_fft_spikes were still queued (round 5: the rows of the
         # next CCD's k-space fill overwritten, a fault or a hang once the side stream ran behind)
-        self._last = (kbuf, rbuf, final, obj_t, kpre_t, rpre_t, bbox, getattr(self, "_spike_list", None), kn)
+        self._last = (kbuf, rbuf, final, obj_t, kpre_t, rpre_t, bbox, getattr(self, "_spike_list", None), kn, im)
         return kspace, rbuf

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import catalog, fft_draw, photon_pooling, stamp
-from ._abi import IMS_OBJ_FAINT, IMS_PROF_KNOTS
+from ._abi import IMS_OBJ_FAINT, IMS_PROF_IMAGE, IMS_PROF_KNOTS
 
 IMAGE_REQ = {"det_name": str}
 IMAGE_OPT = {"size": int, "xsize": int, "ysize": int, "dtype": None, "apply_sky_gradient": bool,
@@ -68,9 +68,10 @@ class LSST_ImageBuilderBase:
 
 
     @staticmethod
-    def _use_fft(sub, nominal, fwhm_total, fft_sb_thresh, kpsf, extra_ktables, fft_knots=False):
+    def _use_fft(sub, nominal, fwhm_total, fft_sb_thresh, kpsf, extra_ktables, fft_knots=False, fft_stamps=False, images=None):
         """FFT or photons for every object (stamp.py:275-277 + get_fft_psf_maybe, psf_utils.py:195-212): GalSim's max_sb
-        of Convolve(object, FFT-mode PSF) from the analytic peaks of the components.  fft_knots: stamp.fft_knots."""
+        of Convolve(object, FFT-mode PSF) from the analytic peaks of the components.  fft_knots: stamp.fft_knots.
+        fft_stamps: stamp.fft_stamps, with `images` the scene's image profiles (the peaks of the FITS-stamp objects)."""
         from . import tables
         kw = {}
         if kpsf:
@@ -82,7 +83,9 @@ class LSST_ImageBuilderBase:
             kw["jac_det"] = sub["mu"]                        # shear preserves area; the lens magnifies it by mu
         if sub.get("box_length") is not None:
             kw["box_area"] = np.asarray(sub["box_length"], dtype=np.float64) * np.asarray(sub["box_width"], dtype=np.float64)
-        return fft_draw.use_fft(nominal, sub["kind"], sub["hlr"], fwhm_total, fft_sb_thresh, fft_knots=fft_knots, **kw)
+        if fft_stamps and images and (np.asarray(sub["kind"]) == catalog.KIND_IMAGE).any():
+            kw["image_peaks"] = fft_draw.image_peaks_per_flux(images, sub["image_index"], sub["image_scale"])
+        return fft_draw.use_fft(nominal, sub["kind"], sub["hlr"], fwhm_total, fft_sb_thresh, fft_knots=fft_knots, fft_stamps=fft_stamps, **kw)
 
     def sky_pixel_areas(self, renderer, use_flux=False):
         """Pixel areas for drawing the sky on a Silicon sensor (`sensor.calculate_pixel_areas(image, use_flux=...)`, which
@@ -151,6 +154,14 @@ class LSST_ImageBuilderBase:
         return renderer.image
 
 
+def _stamp_kw(fft_stamps, scene):
+    """has_kspace_form's keywords for stamp.fft_stamps: nothing while the switch is off (the call is the one of before)"""
+    if not fft_stamps:
+        return {}
+    profiles = getattr(scene, "image_profiles", None) or []
+    return dict(fft_stamps=True, image_sizes=np.array([(im.shape[1], im.shape[0]) for im in profiles], dtype=np.int64).reshape(-1, 2))
+
+
 @dataclasses.dataclass
 class CcdJob:
     """Everything of ONE CCD's `LSST_Image` build that is decided on the host, ahead of the GPU: the rows of the
@@ -161,6 +172,7 @@ class CcdJob:
     nrecalc: Optional[int] = None
     fft_rows: Optional[np.ndarray] = None              # FFT_OBJECT_DTYPE rows sorted by FFT size (fft_draw.build_fft_objects)
     fft_knots: Optional[tuple] = None                  # fft_draw.knot_side_arrays of fft_rows (stamp.fft_knots; None: no RandomKnots row)
+    fft_images: Optional[np.ndarray] = None            # fft_draw.image_side_arrays of fft_rows (stamp.fft_stamps; None: no FITS-stamp row)
     kpsf: Optional[list] = None                        # k-space PSF of the FFT drawer
     extra_ktables: tuple = ()
     diffraction_fft: "object" = None
@@ -206,7 +218,7 @@ def draw_job(renderer, job, realized=None, fft_stream=None, defer=False):
         drawer = fft_draw.FftDrawer(renderer, job.kpsf, add_noise=True, diffraction_fft=job.diffraction_fft,
                                     wavelength=job.wavelength, extra_ktables=job.extra_ktables)
         r_fft = torch.zeros(job.n_fft, dtype=torch.float64, device=renderer.device) if realized is not None else None
-        state = drawer._upload(job.fft_rows, job.fft_knots)
+        state = drawer._upload(job.fft_rows, job.fft_knots, job.fft_images)
         if side is not None:
             side.wait_stream(main)                                # the renderer's scene tables, its zeroed image, the uploads above
         with torch.cuda.stream(side if side is not None else main):
@@ -258,11 +270,13 @@ class LSST_ImageBuilder(LSST_ImageBuilderBase):
 
     def prepare(self, scene, cat, phot_flux, make_objects, fft_sb_thresh=0.0, max_flux_simple=100.0,
                 draw_method="auto", kpsf=None, fwhm_total=0.8, diffraction_fft=None, wavelength=622.2,
-                nrecalc=None, extra_ktables=(), vignetting=None, sky=None, fft_knots=False):
+                nrecalc=None, extra_ktables=(), vignetting=None, sky=None, fft_knots=False, fft_stamps=False):
         """Host half of the draw loop: which objects exist (SkipThisObject for phot_flux == 0, stamp.py:199-202), FFT /
         photons / faint for each (stamp.py:275-336), the rows of both kinds.  Nothing here touches the GPU.
         fft_knots (stamp.fft_knots, an extension, off by default): RandomKnots objects above the threshold take the FFT branch as the
-        reference's do -- unless the PSF has aliases to fold (fft_draw.has_kspace_form)."""
+        reference's do -- unless the PSF has aliases to fold (fft_draw.has_kspace_form).
+        fft_stamps (stamp.fft_stamps, an extension, off by default): the same for FITS-stamp objects (scene.image_profiles), which
+        must also fit the grid their stamp size gives them."""
         n_all = len(cat["x"])
         if self.nobjects is not None:
             n_all = min(n_all, int(self.nobjects))
@@ -276,13 +290,15 @@ class LSST_ImageBuilder(LSST_ImageBuilderBase):
         elif draw_method == "phot":
             is_fft = np.zeros(n_all, dtype=bool)
         else:
-            is_fft = self._use_fft(sub, nominal, fwhm_total, fft_sb_thresh, kpsf, extra_ktables, fft_knots)
+            is_fft = self._use_fft(sub, nominal, fwhm_total, fft_sb_thresh, kpsf, extra_ktables, fft_knots, fft_stamps,
+                                   getattr(scene, "image_profiles", None))
         objects, sizes = make_objects(sub, np.where(phot > 0, phot, 0))
         keep = np.flatnonzero(phot > 0)                       # SkipThisObject for phot_flux == 0 (stamp.py:199-202)
         # knots and FITS stamps have no k-space form here and stay photon-shot; so does a streak longer than its grid (it would wrap)
-        # (knots behind stamp.fft_knots: the structure-factor pass, in the base band only)
-        n_alias = fft_draw.kpsf_alias_order(kpsf, extra_ktables) if fft_knots else 0
-        fft_rows = is_fft[keep] & fft_draw.has_kspace_form(np.asarray(sub["kind"])[keep], objects, fft_knots=fft_knots, n_alias=n_alias)
+        # (knots behind stamp.fft_knots: the structure-factor pass, in the base band only; FITS stamps behind stamp.fft_stamps alike)
+        n_alias = fft_draw.kpsf_alias_order(kpsf, extra_ktables) if (fft_knots or fft_stamps) else 0
+        fft_rows = is_fft[keep] & fft_draw.has_kspace_form(np.asarray(sub["kind"])[keep], objects, fft_knots=fft_knots, n_alias=n_alias,
+                                                           **_stamp_kw(fft_stamps, scene))
         faint = nominal[keep] < max_flux_simple
         objects["flags"] = np.where(faint, objects["flags"] | IMS_OBJ_FAINT, objects["flags"] & ~IMS_OBJ_FAINT)
         fft_flux = np.zeros(len(objects))
@@ -302,6 +318,8 @@ class LSST_ImageBuilder(LSST_ImageBuilderBase):
             job.fft_rows, order = fft_draw.build_fft_objects(fobj, fflux, tables_needed)
             if fft_knots and (fobj["prof_table"] == IMS_PROF_KNOTS).any():
                 job.fft_knots = fft_draw.knot_side_arrays(fobj, order)
+            if fft_stamps and (fobj["prof_table"] == IMS_PROF_IMAGE).any():
+                job.fft_images = fft_draw.image_side_arrays(fobj, order)
             job.fft_index = np.flatnonzero(fft_rows)[order]
             fft_flux[np.flatnonzero(fft_rows)] = fflux
         job.host = dict(sel=sel, keep=keep, sub=sub, nominal=nominal, phot=phot, fft_rows=fft_rows, faint=faint, fft_flux=fft_flux)
@@ -309,7 +327,7 @@ class LSST_ImageBuilder(LSST_ImageBuilderBase):
 
     def build_image(self, renderer, cat, phot_flux, make_objects, fft_sb_thresh=0.0, max_flux_simple=100.0,
                     draw_method="auto", kpsf=None, fwhm_total=0.8, diffraction_fft=None, wavelength=622.2,
-                    nrecalc=None, truth=None, extra_ktables=(), vignetting=None, fft_knots=False):
+                    nrecalc=None, truth=None, extra_ktables=(), vignetting=None, fft_knots=False, fft_stamps=False):
         """The draw loop (imsim/lsst_image.py:342-368 + imsim/stamp.py:411-575).
 
         cat / phot_flux: catalog dict and Poisson-realised fluxes; make_objects(cat, phot) builds the
@@ -318,7 +336,7 @@ class LSST_ImageBuilder(LSST_ImageBuilderBase):
         job = self.prepare(renderer.scene, cat, phot_flux, make_objects, fft_sb_thresh=fft_sb_thresh, max_flux_simple=max_flux_simple,
                            draw_method=draw_method, kpsf=kpsf, fwhm_total=fwhm_total, diffraction_fft=diffraction_fft,
                            wavelength=wavelength, nrecalc=nrecalc, extra_ktables=extra_ktables, vignetting=vignetting,
-                           fft_knots=fft_knots)
+                           fft_knots=fft_knots, fft_stamps=fft_stamps)
         realized = renderer.torch.zeros(job.n_kept, dtype=renderer.torch.float64, device=renderer.device)
         draw_job(renderer, job, realized=realized)
         if truth is not None:
@@ -349,7 +367,7 @@ class LSST_PhotonPoolingImageBuilder(LSST_ImageBuilderBase):
 
     def build_image(self, renderer, cat, phot_flux, make_objects, max_flux_simple=100.0, seed=0, truth=None, fft_sb_thresh=0.0,
                     kpsf=None, fwhm_total=0.8, diffraction_fft=None, wavelength=622.2, extra_ktables=(), vignetting=None,
-                    checkpoint=None, fft_knots=False):
+                    checkpoint=None, fft_knots=False, fft_stamps=False):
         """LSST_PhotonPoolingImageBuilder.buildImage (imsim/photon_pooling.py:29-174): the fluxes of all objects are known
         up front, so the objects are partitioned into FFT / photon-shooting / faint; the FFT objects are drawn FIRST
         (:84-114, in nbatch_fft batches over objects), then the photon batches run through the pooled path."""
@@ -360,11 +378,13 @@ class LSST_PhotonPoolingImageBuilder(LSST_ImageBuilderBase):
         nominal = np.asarray(sub["nominal_flux"])
         objects, _ = make_objects(sub, phot)
         keep = np.flatnonzero(phot > 0)
-        is_fft = self._use_fft(sub, nominal, fwhm_total, fft_sb_thresh, kpsf, extra_ktables, fft_knots)
+        is_fft = self._use_fft(sub, nominal, fwhm_total, fft_sb_thresh, kpsf, extra_ktables, fft_knots, fft_stamps,
+                               getattr(renderer.scene, "image_profiles", None))
         # (the same rule as LSST_ImageBuilder.prepare: knots, FITS stamps and streaks longer than their grid stay with the photons;
-        # knots behind stamp.fft_knots take the FFT branch in the base band)
-        n_alias = fft_draw.kpsf_alias_order(kpsf, extra_ktables) if fft_knots else 0
-        fft_rows = is_fft[keep] & fft_draw.has_kspace_form(np.asarray(sub["kind"])[keep], objects, fft_knots=fft_knots, n_alias=n_alias)
+        # knots behind stamp.fft_knots and FITS stamps behind stamp.fft_stamps take the FFT branch in the base band)
+        n_alias = fft_draw.kpsf_alias_order(kpsf, extra_ktables) if (fft_knots or fft_stamps) else 0
+        fft_rows = is_fft[keep] & fft_draw.has_kspace_form(np.asarray(sub["kind"])[keep], objects, fft_knots=fft_knots, n_alias=n_alias,
+                                                           **_stamp_kw(fft_stamps, renderer.scene))
         modes = stamp.classify(nominal[keep], max_flux_simple)
         modes[fft_rows] = stamp.ProcessingMode.FFT
         realized = torch.zeros(len(objects), dtype=torch.float64, device=renderer.device)
@@ -395,7 +415,8 @@ class LSST_PhotonPoolingImageBuilder(LSST_ImageBuilderBase):
                     fobj, fflux, fft_draw.profile_ktable_ids(renderer.scene, fobj["prof_table"], len(extra_ktables)))
                 r_fft = torch.zeros(len(rows), dtype=torch.float64, device=renderer.device)
                 knots = fft_draw.knot_side_arrays(fobj, order) if fft_knots and (fobj["prof_table"] == IMS_PROF_KNOTS).any() else None
-                drawer.draw(rows, realized=r_fft, knots=knots)
+                images = fft_draw.image_side_arrays(fobj, order) if fft_stamps and (fobj["prof_table"] == IMS_PROF_IMAGE).any() else None
+                drawer.draw(rows, realized=r_fft, knots=knots, images=images)
                 realized.index_add_(0, torch.from_numpy(batch[order]).to(renderer.device), r_fft)
                 fft_flux[batch] = fflux
             if checkpoint is not None:

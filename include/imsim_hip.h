@@ -697,6 +697,21 @@ int  ims_knot_positions(uint64_t seed, const ims_fft_object_t* objects_dev, int6
 int  ims_fft_knots_factor(const ims_fft_params_t* params, const ims_fft_object_t* objects_dev, const int32_t* knot_rows_dev,
                           int64_t n_knot_rows, int32_t max_nfft, const int32_t* n_knots_dev, const int64_t* knot_offset_dev,
                           const double* knot_xy_dev, double* kbuf, void* stream);
+/* FITS stamps (IMS_PROF_IMAGE, galsim.InterpolatedImage) on the FFT branch (base band only: n_alias == 0).  Between ims_fft_kspace_fill
+ * (which fills a stamp object as a point, prof_ktable IMS_PROF_POINT) and the inverse transform: the half spectrum of every row listed in
+ * image_rows_dev (int32 [n_image_rows], indices into objects_dev) is multiplied in place by
+ *     F(k) = [sum_m w_m exp(-i k . d_m)] Qhat(q_u p / 2 pi) Qhat(q_v p / 2 pi),   q = jac^T k,   p = the row's prof_scale,
+ * d_m = jac (p (a + 1/2 - w / 2), p (b + 1/2 - h / 2)), Qhat the transform of the interpolant (interpolant 1: GalSim's Quintic;
+ * 0: nearest, sinc).  Side arrays, no struct field: row_image_dev int32 [n_objects] (the image of every FFT row, -1 = none; every listed
+ * row has one), and per image profile, for all n_images of a scene: image_size_dev int32 [n_images][2] (w, h), image_offset_dev int64
+ * [n_images + 1] (prefix sum of the number of positive pixels), pixel_ab_dev int32 [total][2] (column a, row b of every positive pixel,
+ * row-major) and pixel_w_dev double [total] (the pixel over the sum of the image's positive pixels).  max_nfft: the largest nfft among
+ * the listed rows.  Rows not listed are neither read nor written; n_image_rows == 0 launches nothing.  The sum runs over the pixels
+ * ascending with one association: the result does not depend on the launch geometry. */
+int  ims_fft_image_factor(const ims_fft_params_t* params, const ims_fft_object_t* objects_dev, const int32_t* image_rows_dev,
+                          int64_t n_image_rows, int32_t max_nfft, const int32_t* row_image_dev, int32_t n_images,
+                          const int32_t* image_size_dev, const int64_t* image_offset_dev, const int32_t* pixel_ab_dev,
+                          const double* pixel_w_dev, int32_t interpolant, double* kbuf, void* stream);
 /* Optional spike step between the inverse transform and ims_fft_finish: clip rbuf_in, find each object's
  * saturated bounding box (bbox_dev: int32 [n_objects][4] scratch = rowmin,rowmax,colmin,colmax), write
  * the spiked image to rbuf_out.  No-op copy when params->spikes.enabled == 0. */
