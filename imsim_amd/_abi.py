@@ -333,6 +333,11 @@ CR_SPAN_STRUCT_INDEX, CR_HIT_STRUCT_INDEX = 26, 27
 # and the optical phase screen (the oracle has no such component)
 OPTICAL_SCREEN_STRUCT_INDEX, ATMOSPHERE_OPTICAL_STRUCT_INDEX = 28, 29
 
+class PsfProfile(C.Structure):
+    """ims_psf_profile_t: the bins of ims_psf_profile (device pointers to the squared radial edges and the sector directions)"""
+    _fields_ = [("n_r", c_i32), ("n_phi", c_i32), ("r2_edge_dev", c_vp), ("dir_dev", c_vp)]
+
+
 # every symbol include/imsim_hip.h declares
 EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_info", "ims_known_optics_layout", "ims_photon_kernel_variant",
            "ims_tuning_defaults", "ims_get_tuning", "ims_set_tuning", "ims_shoot_accumulate",
@@ -346,7 +351,7 @@ EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_
            "ims_count_inexact", "ims_struct_size", "ims_test_math", "ims_opd", "ims_opd_perturbed",
            "ims_paint_cosmic_rays", "ims_test_optical_screen", "ims_trace_field_points", "ims_trace_field_points_perturbed",
            "ims_object_spectra", "ims_psf_moments", "ims_knot_positions", "ims_fft_knots_factor",
-           "ims_fft_image_factor"]
+           "ims_fft_image_factor", "ims_psf_profile"]
 
 _LIB_PATH = tuning.env("IMSIM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libimsim_hip.so")
 _lib = None
@@ -461,6 +466,7 @@ def load():
     lib.ims_trace_field_points.argtypes = [c_vp, c_vp, c_vp, c_i64, c_d, c_vp, c_i32, c_vp, c_vp, c_vp]
     lib.ims_trace_field_points_perturbed.argtypes = [c_vp, c_vp, c_vp, c_i64, c_d, c_vp, c_i32, c_vp, c_vp, c_vp]
     lib.ims_psf_moments.argtypes = [C.POINTER(RenderParams), c_i32, c_vp, c_vp, c_vp, c_vp]
+    lib.ims_psf_profile.argtypes = [C.POINTER(RenderParams), c_i32, C.POINTER(PsfProfile), c_vp, c_vp, c_vp, c_vp]
     lib.ims_object_spectra.argtypes = [c_vp, c_vp, c_vp, c_vp, c_i32, c_d, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,
                                        c_i32, c_vp, c_vp, c_i64, c_vp]
     _lib = lib

@@ -20,7 +20,7 @@ import numpy as np
 import yaml
 
 from . import _abi, atm_psf, catalog, configs, diffraction, fft_draw, instcat, lsst_image, optical_system, optics as opticsmod
-from . import cosmic_rays, flat, opd as opdmod, parallel, psf_map as psfmapmod, readout, sensor as sensormod, tables, treerings, truth as truthmod, tuning
+from . import cosmic_rays, flat, opd as opdmod, parallel, psf_map as psfmapmod, psf_profile as psfprofmod, readout, sensor as sensormod, tables, treerings, truth as truthmod, tuning
 from .engine import Scene, SensorSetup, make_slots
 from .lsst_image import GalSimConfigError
 
@@ -849,7 +849,7 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     if itype not in valid_image_types:
         raise GalSimConfigError(f"Invalid image type {itype}")
     if itype == "LSST_Flat":
-        for k in ("opd", "sag", "psf_map"):        # a flat has no telescope to trace, and no PSF
+        for k in ("opd", "sag", "psf_map", "psf_profile"):        # a flat has no telescope to trace, and no PSF
             if k in out:
                 res.ignored.append(f"output.{k}")
         return _process_flat(cfg, ev, image, res, device, data_dir)
@@ -867,6 +867,13 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     opd_kw = parse_opd(out["opd"], ev) if "opd" in out else None     # config errors before any GPU work
     psf_map_kw = psfmapmod.parse_config(out["psf_map"], ev) if "psf_map" in out else None
     psf_maps = {}                                                       # file name -> [(cube, header)], one per CCD
+    psf_profile_kw = psfprofmod.parse_config(out["psf_profile"], ev) if "psf_profile" in out else None
+    psf_profiles = {}                                                   # file name -> [(cube, header, summary, header)], one per CCD
+    if psf_profile_kw is not None and psf_profile_kw["stage"] == "ops":
+        for op in stamp_cfg.get("photon_ops", []) or []:
+            if isinstance(op, dict) and op.get("type") == "BandpassRatio":
+                raise GalSimConfigError("output.psf_profile counts photons unweighted: stage ops cannot run a chain with a BandpassRatio "
+                                        "operator (stamp.photon_ops), whose photons carry unequal flux")
     catalogs = parse_catalogs(out, ev, itype)
     crs = parse_cosmic_rays(out, ev, data_dir)
     parse_atm_psf_options(inp.get("atm_psf"), stamp_cfg, ev, data_dir, res, itype, cfg.get("psf"))
@@ -1118,6 +1125,13 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
             wl, thr = tables.synthetic_r_band()
             psf_maps.setdefault(fn, []).append(psfmapmod.ccd_map(ctx.scene, ctx.det_name, wl_eff=tables.effective_wavelength(wl, thr),
                                                                  device=device, **psf_map_kw))
+        if psf_profile_kw is not None:
+            # output.psf_profile: radial / azimuthal histograms of the same photons on the same grid
+            pp = out["psf_profile"]
+            fn = os.path.join(str(ev.value(pp.get("dir", out.get("dir", "")))), str(ev.value(pp["file_name"])))
+            wl, thr = tables.synthetic_r_band()
+            psf_profiles.setdefault(fn, []).append(psfprofmod.ccd_profile(ctx.scene, ctx.det_name, wl_eff=tables.effective_wavelength(wl, thr),
+                                                                          device=device, **psf_profile_kw))
         done[ctx.det] = (img, ctx.truth, ctx.det_name, sub)
 
     # Several CCDs of LSST_Image type go through the overlapped focal-plane path (focal_plane.render_focal_plane, the per-CCD
@@ -1161,6 +1175,9 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
         res.files += sub.files
     for fn, hdus in psf_maps.items():                    # one image HDU per CCD that names the file
         psfmapmod.write(fn, hdus)
+        res.files.append(fn)
+    for fn, hdus in psf_profiles.items():                # two image HDUs (counts, summary) per CCD that names the file
+        psfprofmod.write(fn, hdus)
         res.files.append(fn)
     if "sag" in out and rank == 0:
         # the telescope input of the reference holds the camera turned by the rotator (imsim/telescope_loader.py:242-246)

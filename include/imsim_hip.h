@@ -1153,6 +1153,30 @@ int  ims_trace_field_points_perturbed(const ims_optics_perturbed_t* optics_dev, 
 int  ims_psf_moments(const ims_render_params_t* params, int32_t stage, double* partial_dev, double* sums_dev, int64_t* counts_dev,
                      void* stream);
 
+/* ---- radial and azimuthal histograms of the delivered PSF at a table of field points ----
+ * The rows, the stages and the photons are those of ims_psf_moments: photon k of a row is the same photon, bit for bit, and
+ * (dx, dy) the same offset from the row's nominal position.  With centre_dev (f64 [n][2], or NULL) the row's centre is then
+ * subtracted, one f64 subtraction per axis -- e.g. the centroid an earlier ims_psf_moments call measured.  A photon whose flux
+ * is 0 is counted in dropped_dev[i] and in no bin; every other photon adds 1 to one bin of counts_dev[i][radial][sector]
+ * (int64 [n][n_r + 2][n_phi + 1]; its flux is not applied, and a chain with an IMS_OP_BANDPASS_RATIO operator is refused in
+ * stage 2 with IMS_ERR_UNSUPPORTED).  Both outputs are zeroed by the call.
+ * The binning uses f64 products, sums and comparisons only, each rounded once (no contraction, no trigonometry):
+ *   r2 = fl(fl(dx dx) + fl(dy dy));  radial index = the number of edges e of r2_edge_dev with e <= r2:
+ *        0 underflow, 1 .. n_r the bins [e_{i-1}, e_i), n_r + 1 overflow
+ *   t_b = fl(fl(c_b dy) - fl(s_b dx)) for direction b of dir_dev;  sector index = the first b, ascending, with t_b >= 0 and
+ *        t_{b+1} < 0 (b + 1 wrapping to 0): the sector from direction b counter-clockwise to the next; n_phi when no b
+ *        qualifies (a photon on the centre, in a rounding gap between two sectors, or not a number).  n_phi = 0: one column.
+ * The counts are integer sums: a row's table is the same in every call, whatever the launch geometry, the other rows of the
+ * call and their order.  Added in ABI version 22 without changing any existing struct or function, so the version number stays. */
+typedef struct ims_psf_profile {
+    int32_t n_r;                     /* radial bins, 1 .. 64 */
+    int32_t n_phi;                   /* sectors, 0 or 3 .. 64 */
+    const double* r2_edge_dev;       /* device, [n_r + 1]: squared radii, strictly ascending */
+    const double* dir_dev;           /* device, [n_phi][2]: the sectors' start directions (cos, sin), counter-clockwise; NULL with n_phi 0 */
+} ims_psf_profile_t;
+int  ims_psf_profile(const ims_render_params_t* params, int32_t stage, const ims_psf_profile_t* spec, const double* centre_dev,
+                     int64_t* counts_dev, int64_t* dropped_dev, void* stream);
+
 /* ---- cosmic rays on the e-image (imsim/cosmic_rays.py:paint_cr) ----
  * A footprint of the catalog is a run of spans; a hit paints one footprint (or a run of its spans) at (x0, y0).  Every span
  * pixel lands on image[y0 + row][x0 + col + k] += values[value_offset + k] (k = 0 .. n-1); pixels off the image are dropped.
