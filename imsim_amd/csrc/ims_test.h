@@ -5,7 +5,7 @@
 #pragma once
 
 // device math probe for the parity tests (which: 0 log,1 exp,2 sincos2pi,3 atan,4 sincos,5 tanh,6 gauss,7 dsqrt_n,8 ddiv of pairs,9 dsqrt0,
-// 10 sincos2pi of a word,11 log of a word,12 gauss_word_cos of pairs,13 dlgamma)
+// 10 sincos2pi of a word,11 log of a word,12 gauss_word_cos of pairs,13 dlgamma,14 atan2 of pairs,15 pow of pairs,16 Philox block of quads)
 __global__ void k_test_math(int which, const double* __restrict__ in, double* __restrict__ out, int64_t n,
                             uint64_t seed, int64_t obj, uint32_t slot)
 {
@@ -30,6 +30,19 @@ __global__ void k_test_math(int which, const double* __restrict__ in, double* __
     case 12: out[i] = gauss_word_cos((uint32_t)in[2 * i], (uint32_t)in[2 * i + 1]); break;
     // log Gamma of the Poisson deviate's acceptance test (x > 0)
     case 13: out[i] = dlgamma(in[i]); break;
+    case 14: out[i] = datan2(in[2 * i], in[2 * i + 1]); break;       // pairs (y, x)
+    case 15: out[i] = dpow(in[2 * i], in[2 * i + 1]); break;         // pairs (x, y)
+    // the raw Philox block of four integer-valued doubles (photon low word, photon high word, slot, object low word); the seed and
+    // the object's high word come through `seed` and `obj` (its low word is replaced by the point's): four words out
+    case 16: {
+        const uint64_t photon = (uint64_t)(uint32_t)in[4 * i] | ((uint64_t)(uint32_t)in[4 * i + 1] << 32);
+        const uint64_t id = ((uint64_t)obj & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)in[4 * i + 3];
+        // an empty cache is marked by slot 0xFFFFFFFF (rng_reset), which no kernel uses but the second Random123 vector has:
+        // mark it with another slot than the one asked for
+        const uint32_t slot_i = (uint32_t)in[4 * i + 2];
+        Rng r; rng_reset(r); r.slot = ~slot_i; rng_block(r, seed, (int64_t)id, (int64_t)photon, slot_i);
+        for (int j = 0; j < 4; ++j) out[4 * i + j] = (double)r.w[j];
+        break; }
     }
 }
 

@@ -12,6 +12,7 @@ Mathis 1989 (with O'Donnell's 1994 optical coefficients, the `CCM` model the cat
 by a few per cent of A(lambda) in the optical.
 """
 import gzip
+import math
 import os
 
 import numpy as np
@@ -99,6 +100,26 @@ def extinction_factor(wave_nm, av, rv):
         sel = rv == r
         out[sel] = 10.0 ** (-0.4 * av[sel, None] * ccm89(wave_nm, r)[None, :])
     return out
+
+
+EXP_DOMAIN = 690.0          # |x| the spec's exp is specified for (693.49, the cap of its power-of-two scale)
+
+
+def check_extinction(av, rv, ext_a, ext_b):
+    """Refuse (A_v, R_v) values with which the device's exp(-0.4 ln 10 A_v (a + b / R_v)) (ims_sed.h) would leave the domain of
+    the spec's exp: a value that is not finite, R_v = 0, or an exponent beyond +-EXP_DOMAIN anywhere on the grid.  The kernel
+    itself does not check; out of domain its exp returns NaN or a capped value."""
+    av = np.atleast_1d(np.asarray(av, dtype=np.float64))
+    rv = np.atleast_1d(np.asarray(rv, dtype=np.float64))
+    bad = ~(np.isfinite(av) & np.isfinite(rv) & (rv != 0.0))
+    if not bad.any() and len(av):
+        urv, inv = np.unique(rv, return_inverse=True)
+        curve = np.abs(np.asarray(ext_a)[None, :] + np.asarray(ext_b)[None, :] / urv[:, None]).max(axis=1)
+        bad = ~(0.4 * math.log(10.0) * np.abs(av) * curve[inv] <= EXP_DOMAIN)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"extinction: A_v = {av[i]}, R_v = {rv[i]} (object {i}, {int(bad.sum())} in all) puts "
+                         f"10^(-0.4 A(lambda)) outside exp's domain")
 
 
 class SedLibrary:
@@ -223,6 +244,7 @@ def object_spectra_hip(names, redshift, mw_av, mw_rv, bandpass_wave, bandpass_th
                           np.asarray(mw_av, dtype=np.float64), np.asarray(mw_rv, dtype=np.float64)])
     if len(f64) != 4 * len(grid) + 2 * len(wave) + 3 * n:
         raise ValueError("object_spectra_hip: redshift, mw_av and mw_rv need one value per name")
+    check_extinction(mw_av, mw_rv, ext_a, ext_b)
     d64 = torch.from_numpy(f64).to(dev)
     parts = torch.split(d64, [len(grid)] * 4 + [len(wave)] * 2 + [n] * 3)
     d_off = torch.from_numpy(offset).to(dev)

@@ -42,6 +42,7 @@ def load():
         lib.orc_sensor_init_boundaries.argtypes = [C.c_void_p, C.c_int, C.c_int]
         lib.orc_sensor_update_distortions.argtypes = [C.c_void_p, C.c_int, C.c_int]
         lib.orc_test_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+        lib.orc_test_words.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_int64]
         lib.orc_fft_kspace_fill.argtypes = [C.POINTER(_abi.FftParams), C.c_void_p, C.c_int64, C.c_void_p]
         lib.orc_fft_finish.argtypes = [C.POINTER(_abi.FftParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.orc_test_poisson.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_int64]
@@ -62,11 +63,15 @@ def load():
     return _lib
 
 
-def math_probe(which, x):
+def math_probe(which, x, seed=0, obj=0):
     """Evaluate the spec's elementary function `which` (see ims_test_math) on the CPU."""
     lib = load()
     x = np.ascontiguousarray(x, dtype=np.float64)
-    n = x.size // 2 if which == 12 else x.size          # 12: (w0, w1) pairs in, one deviate out
+    if which == 16:                                      # (photon lo, photon hi, slot, object lo) quads in, four words out
+        out = np.empty(x.size)
+        lib.orc_test_words(x.ctypes.data, out.ctypes.data, x.size // 4, seed, obj)
+        return out
+    n = x.size // 2 if which in (12, 14, 15) else x.size          # pairs in, one value out
     m = 2 if which in (2, 4, 10) else 1
     out = np.empty(n * m)
     lib.orc_test_math(which, x.ctypes.data, out.ctypes.data, n)

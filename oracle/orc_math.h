@@ -88,6 +88,25 @@ static inline double orc_u01_open(uint64_t k) { return (double)(k + 1) * 0x1.0p-
 #define ORC_PI_2 1.57079632679489661923
 #define ORC_PI_4 0.78539816339744830962
 
+/* double -> integer as gfx950 converts: towards zero, saturating at the ends of the integer's range, NaN -> 0.  A plain C cast is
+ * undefined there (x86 gives INT_MIN for all of them), and the functions below are specified for every input, so they convert
+ * with these.  The device forms the 64-bit result from two 32-bit conversions and gives 0x7FFFFFFF00000000 where this gives
+ * INT64_MAX; orc_exp only compares the result with +-1000. */
+static inline int64_t orc_sat_i64(double x)
+{
+    if (x != x) return 0;
+    if (x >= 0x1.0p63) return INT64_MAX;
+    if (x <= -0x1.0p63) return INT64_MIN;
+    return (int64_t)x;
+}
+static inline int32_t orc_sat_i32(double x)
+{
+    if (x != x) return 0;
+    if (x >= 2147483647.0) return INT32_MAX;
+    if (x <= -2147483648.0) return INT32_MIN;
+    return (int32_t)x;
+}
+
 /* natural log, x > 0 normal */
 static inline double orc_log(double x)
 {
@@ -135,7 +154,7 @@ static inline double orc_exp(double x)
     p = orc_fma(p, r, 0.5);
     p = orc_fma(p, r, 1.0);
     p = orc_fma(p, r, 1.0);
-    int64_t k = (int64_t)kf;
+    int64_t k = orc_sat_i64(kf);
     if (k < -1000) return 0.0;
     if (k > 1000) k = 1000;
     double scale = orc_from_bits((uint64_t)(k + 1023) << 52);
@@ -177,7 +196,7 @@ static inline void orc_sincos2pi(double u, double* s, double* c)
     double r = orc_fma(-0.25, qf, u);
     double t = r * ORC_TWO_PI;
     double sk = orc_sin_kernel(t), ck = orc_cos_kernel(t);
-    int q = (int)qf & 3;
+    int q = orc_sat_i32(qf) & 3;
     if (q == 0) { *s = sk; *c = ck; }
     else if (q == 1) { *s = ck; *c = -sk; }
     else if (q == 2) { *s = -sk; *c = -ck; }
@@ -190,8 +209,14 @@ static inline void orc_sincos(double x, double* s, double* c)
     orc_sincos2pi(u, s, c);
 }
 
+/* The device's lean division (ddiv) forms its residuals with the negated denominator, so a NaN that reaches it as the denominator
+ * leaves with its sign bit inverted, where the plain division here passes it on unchanged.  Out of domain the two sides must give
+ * the same bits, so the two functions that divide by a function of their argument state that: */
+static inline double orc_nan_through_ddiv(double v) { return orc_from_bits(orc_bits(v) ^ 0x8000000000000000ull); }
+
 static inline double orc_atan(double x)
 {
+    if (x != x) return orc_nan_through_ddiv(x);
     double ax = x < 0.0 ? -x : x;
     double base = 0.0, sign = 1.0;
     double a = ax;
@@ -235,6 +260,7 @@ static inline double orc_tanh_pos(double x)   /* x >= 0 */
 {
     if (x > 20.0) return 1.0;
     double e = orc_exp(-2.0 * x);
+    if (e != e) return orc_nan_through_ddiv(e);          /* x = NaN, and x = -inf through exp(+inf) */
     return (1.0 - e) / (1.0 + e);
 }
 static inline double orc_pow(double x, double y) { return orc_exp(y * orc_log(x)); }

@@ -87,7 +87,20 @@ void orc_test_math(int which, const double* in, double* out, int64_t n)
         case 11: out[i] = orc_log_w((uint32_t)in[i]); break;
         case 12: out[i] = orc_gauss_word_cos((uint32_t)in[2 * i], (uint32_t)in[2 * i + 1]); break;
         case 13: out[i] = orc_lgamma(in[i]); break;
+        case 14: out[i] = orc_atan2(in[2 * i], in[2 * i + 1]); break;
+        case 15: out[i] = orc_pow(in[2 * i], in[2 * i + 1]); break;
         }
+    }
+}
+/* probe 16 of ims_test_math: the raw block of (photon low word, photon high word, slot, object low word) quads; the seed and the
+ * object's high word come from the arguments */
+void orc_test_words(const double* in, double* out, int64_t n, uint64_t seed, int64_t obj)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        uint64_t photon = (uint64_t)(uint32_t)in[4 * i] | ((uint64_t)(uint32_t)in[4 * i + 1] << 32);
+        uint64_t id = ((uint64_t)obj & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)in[4 * i + 3];
+        orc_words_t w = orc_words(seed, (int64_t)id, (int64_t)photon, (uint32_t)in[4 * i + 2]);
+        for (int j = 0; j < 4; ++j) out[4 * i + j] = (double)w.w[j];
     }
 }
 void orc_test_philox(uint32_t c[4], uint32_t k0, uint32_t k1) { orc_philox4x32_10(c, k0, k1); }

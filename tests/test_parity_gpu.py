@@ -20,12 +20,13 @@ def torch_cuda():
 
 def _dev_math(torch, which, x, seed=0, obj=0, slot=0, n=None):
     lib = _abi.load()
-    m = 2 if which in (2, 4, 6, 10) else 1
+    m = 2 if which in (2, 4, 6, 10) else 4 if which == 16 else 1
     if which == 6:
         xin = torch.zeros(1, dtype=torch.float64, device="cuda")
     else:
         xin = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).cuda()
-        n = xin.numel() // 2 if which == 12 else xin.numel()
+        # 8, 12, 14, 15: pairs in, one value out; 16: (photon lo, photon hi, slot, object lo) quads in, four words out
+        n = xin.numel() // 2 if which in (8, 12, 14, 15) else xin.numel() // 4 if which == 16 else xin.numel()
     out = torch.empty(n * m, dtype=torch.float64, device="cuda")
     _abi.check(lib.ims_test_math(which, xin.data_ptr(), out.data_ptr(), n, seed, obj, slot, None))
     torch.cuda.synchronize()
