@@ -8,8 +8,9 @@
 // pixel-boundary state and the image lines they touch.
 //
 // ONE translation unit, written as sections: ims_host.h (the library's host state and the helpers every entry point uses),
-// this file, then ims_exchange.h and ims_test.h.  A section holds its kernels, its static host helpers and its own extern "C"
-// block, and needs only what is included before it (DESIGN.md has the file map).
+// this file, then one file per subsystem that has been cut out of it (ims_readout.h .. ims_test.h).  A section holds its kernels,
+// its static host helpers and its own extern "C" block, and needs only what is included before it (DESIGN.md has the file map
+// and says what is still here).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -2660,352 +2661,6 @@ __global__ __launch_bounds__(256) void k_fft_finish(const ims_fft_params_t P, co
     });
 }
 
-// ---------------- CCD readout (imsim/readout.py:413-478, imsim/bleed_trails.py) ----------------
-constexpr long long READOUT_ID_BASE = 0x7E00000000ll;   // object id space of the read-noise streams (+ amp index)
-
-// span[4 x + 2 half + {0,1}]: first / last saturated row of the channel (relative to the channel's first row)
-__global__ __launch_bounds__(256) void k_readout_span_init(int* __restrict__ span, int nx)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x < nx) { span[4 * x] = 0x7FFFFFFF; span[4 * x + 1] = -1; span[4 * x + 2] = 0x7FFFFFFF; span[4 * x + 3] = -1; }
-}
-
-__global__ __launch_bounds__(256) void k_readout_flags(const double* __restrict__ image, unsigned char* __restrict__ flags,
-                                                       int* __restrict__ span, int nx, int ny, double full_well, int midline_stop)
-{
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= (int64_t)nx * ny) return;
-    const bool sat = image[p] > full_well;
-    flags[p] = sat ? 1 : 0;
-    if (sat) {                                   // rare: a few hundred pixels of a CCD
-        const int x = (int)(p % nx), y = (int)(p / nx);
-        const int ymid = ny / 2;
-        const int half = (midline_stop && y >= ymid) ? 1 : 0;
-        const int yl = half ? y - ymid : y;
-        atomicMin(&span[4 * x + 2 * half], yl);
-        atomicMax(&span[4 * x + 2 * half + 1], yl);
-    }
-}
-
-// BleedCharge.__call__ (bleed_trails.py:117-152): returns true once the excess is used up
-__device__ __forceinline__ bool bleed_into(double* __restrict__ c, int64_t stride, int n, int ypix, double full_well, double& excess)
-{
-    if (ypix >= 0 && ypix < n) {
-        const double room = full_well - c[(int64_t)ypix * stride];
-        const double b = room < excess ? room : excess;
-        c[(int64_t)ypix * stride] = c[(int64_t)ypix * stride] + b;
-        excess = excess - b;
-    } else if (ypix < 0) {
-        excess = excess - (full_well < excess ? full_well : excess);      // leaves through the serial register
-    }
-    return excess == 0.0;
-}
-
-// one thread per channel (a column, or half a column with the midline stop); neighbouring threads walk neighbouring
-// columns, so every step of the walk is one coalesced row access
-__global__ __launch_bounds__(256) void k_readout_bleed(double* __restrict__ image, const unsigned char* __restrict__ flags,
-                                                       const int* __restrict__ span, int nx, int ny, double full_well,
-                                                       int midline_stop)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n_half = midline_stop ? 2 : 1;
-    if (t >= nx * n_half) return;
-    const int x = t % nx, half = t / nx;
-    const int ymid = ny / 2;
-    const int ylo = (midline_stop && half == 1) ? ymid : 0;
-    const int n = midline_stop ? (half == 0 ? ymid : ny - ymid) : ny;
-    double* c = image + (int64_t)ylo * nx + x;
-    const unsigned char* f = flags + (int64_t)ylo * nx + x;
-    // runs are found on the ORIGINAL flags: only the rows between the first and the last saturated pixel need a look
-    int y = span[4 * x + 2 * half];
-    const int y_last = span[4 * x + 2 * half + 1];
-    while (y <= y_last) {
-        // the way to the next saturated row, eight rows' flags at a time (independent loads: the walk used to wait for every
-        // single byte before it asked for the next)
-        unsigned char fl[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) fl[q] = (y + q <= y_last) ? f[(int64_t)(y + q) * nx] : (unsigned char)0;
-        int skip = 0;
-        while (skip < 8 && !fl[skip]) ++skip;
-        y += skip;
-        if (skip == 8) continue;
-        const int y0 = y;
-        while (y < n && f[(int64_t)y * nx]) ++y;
-        const int y1 = y;
-        double excess = 0.0;
-        for (int k = y0; k < y1; ++k) excess = excess + c[(int64_t)k * nx];
-        excess = excess - (double)(y1 - y0) * full_well;
-        for (int k = y0; k < y1; ++k) c[(int64_t)k * nx] = full_well;
-        const int reach = y0 > n - y1 ? y0 : n - y1;
-        for (int dy = 0; dy < reach; ++dy) {
-            if (bleed_into(c, nx, n, y0 - dy - 1, full_well, excess)) break;
-            if (bleed_into(c, nx, n, y1 + dy, full_well, excess)) break;
-        }
-    }
-}
-
-// e-image pixel read out at position (u, v) of amp a's imaging section, in ADU (float32 like the reference's arrays)
-__device__ __forceinline__ float amp_adu(const double* __restrict__ image, int nx, const ims_readout_t& ro, int a, int u, int v)
-{
-    const ims_amp_t& A = ro.amps[a];
-    const int sx = A.flip_x ? ro.seg_w - 1 - u : u;
-    const int sy = A.flip_y ? ro.seg_h - 1 - v : v;
-    const float e = (float)image[(int64_t)(A.y0 + sy) * nx + (A.x0 + sx)];
-    return e / A.gain;
-}
-
-// grid (raw_w / 64, raw_h / 4, n_amps), block (64, 4)
-// grid (raw_w / 64, raw_h / 4), block (64, 4): a thread forms position (rx, ry) of ALL amplifiers' raw segments -- crosstalk makes every
-// amplifier's pixel there a sum over the sixteen pixels at that position, which were read sixteen times (once per output amplifier:
-// 2.1 GB for a 131-MB image) and are read once now; the sums are the same sums (ascending source amplifier, zero coefficients skipped)
-__global__ __launch_bounds__(256) void k_readout_segments(const double* __restrict__ image, int nx, const ims_readout_t ro,
-                                                          float* __restrict__ seg)
-{
-    const int rx = blockIdx.x * 64 + threadIdx.x, ry = blockIdx.y * 4 + threadIdx.y;
-    if (rx >= ro.raw_w || ry >= ro.raw_h) return;
-    const int u = rx - ro.data_x0, v = ry - ro.data_y0;
-    const bool inside = u >= 0 && u < ro.seg_w && v >= 0 && v < ro.seg_h;
-    float e[IMS_MAX_AMPS];
-#pragma unroll
-    for (int a = 0; a < IMS_MAX_AMPS; ++a) e[a] = (inside && a < ro.n_amps) ? amp_adu(image, nx, ro, a, u, v) : 0.0f;
-#pragma unroll
-    for (int a = 0; a < IMS_MAX_AMPS; ++a) {
-        if (a >= ro.n_amps) break;
-        float out = 0.0f;
-        if (inside) {
-            out = e[a];
-            if (ro.has_xtalk) {
-                float sum = 0.0f;
-#pragma unroll
-                for (int j = 0; j < IMS_MAX_AMPS; ++j) {
-                    if (j >= ro.n_amps) break;
-                    const float x = ro.xtalk[a * IMS_MAX_AMPS + j];
-                    if (x != 0.0f) sum = sum + x * e[j];          // a zero coefficient adds exactly nothing
-                }
-                out = out + sum;
-            }
-        }
-        seg[((int64_t)a * ro.raw_h + ry) * ro.raw_w + rx] = out;
-    }
-}
-
-// grid (raw_w / 64, raw_h / 4, n_amps), block (64, 4): a wavefront is 64 neighbouring columns of one row, so every tap
-// of the parallel direction is one coalesced 256-B row access and the four rows of a workgroup share their taps in L1;
-// no integer division anywhere.
-// NB > 0: the band width is known at compile time (the reference's ntransfers = 20: 21 taps); pixels with a full
-// set of taps take an unrolled path whose 2 x 21 loads are all in flight before the first use.
-template <int NB>
-__global__ __launch_bounds__(256) void k_readout_cte(const float* __restrict__ src, float* __restrict__ dst, int raw_w, int raw_h,
-                                                     const double* __restrict__ band, int n_band, int axis)
-{
-    const int rx = blockIdx.x * 64 + threadIdx.x, ry = blockIdx.y * 4 + threadIdx.y;
-    // serial direction: every lane has a row of weights of its own (its column's) -- the workgroup's 64 rows of weights are one
-    // contiguous piece of the band matrix, staged through LDS once instead of 21 scattered 8-byte loads per lane and row
-    __shared__ double wl[64 * (NB > 0 ? NB : 1)];
-    const bool staged = NB > 0 && axis == 1;
-    if (staged) {
-        const int i0 = blockIdx.x * 64;
-        for (int e = threadIdx.y * 64 + threadIdx.x; e < 64 * NB; e += 256)
-            wl[e] = (i0 + e / NB < raw_w) ? band[(int64_t)i0 * NB + e] : 0.0;
-        __syncthreads();
-    }
-    if (rx >= raw_w || ry >= raw_h) return;
-    const int p = ((int)blockIdx.z * raw_h + ry) * raw_w + rx;
-    const int i = axis == 0 ? ry : rx;
-    const int step = axis == 0 ? raw_w : 1;
-    const int dmax = i < n_band - 1 ? i : n_band - 1;
-    const double* w = band + i * n_band;
-    const double* ws = wl + threadIdx.x * (NB > 0 ? NB : 1);
-    double acc = 0.0;
-    if (NB > 0 && i >= NB - 1) {
-        float v[NB > 0 ? NB : 1];
-        double ww[NB > 0 ? NB : 1];
-#pragma unroll
-        for (int d = 0; d < NB; ++d) v[d] = src[p - d * step];
-        if (staged) {
-#pragma unroll
-            for (int d = 0; d < NB; ++d) ww[d] = ws[d];
-        } else {
-#pragma unroll
-            for (int d = 0; d < NB; ++d) ww[d] = w[d];
-        }
-#pragma unroll
-        for (int d = NB - 1; d >= 0; --d) acc = acc + ww[d] * (double)v[d];
-    } else if (staged) {
-        for (int d = dmax; d >= 0; --d) acc = acc + ws[d] * (double)src[p - d * step];
-    } else {
-        for (int d = dmax; d >= 0; --d) acc = acc + w[d] * (double)src[p - d * step];
-    }
-    dst[p] = (float)acc;
-}
-
-// The read-noise deviates of pixels 2 m and 2 m + 1 of an amplifier are the two Gaussians of ONE counter block: a thread forms the
-// block once and finishes both pixels (segments of an even number of pixels; the single-pixel kernel below did the block twice).
-__global__ __launch_bounds__(256) void k_readout_finish_pairs(const float* __restrict__ seg, const ims_readout_t ro, uint64_t seed,
-                                                              int32_t* __restrict__ out)
-{
-    const int64_t per = (int64_t)ro.raw_w * ro.raw_h;
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       // pair number over all amplifiers
-    if (2 * m >= per * ro.n_amps) return;
-    const int64_t p = 2 * m;
-    const int a = (int)(p / per);
-    const int64_t q = p - (int64_t)a * per;                                 // even
-    typedef float fvec2 __attribute__((ext_vector_type(2)));
-    typedef int ivec2 __attribute__((ext_vector_type(2)));
-    const fvec2 sv = *(const fvec2*)(seg + p);
-    Rng r;
-    rng_reset(r);
-    rng_block(r, seed, READOUT_ID_BASE + a, q >> 1, 0u);
-    double g0, g1;
-    gauss_words(r.w[0], r.w[1], g0, g1);
-    float v0 = sv.x + ro.amps[a].bias_level, v1 = sv.y + ro.amps[a].bias_level;
-    v0 = v0 + (float)((double)ro.amps[a].read_noise * g0);
-    v1 = v1 + (float)((double)ro.amps[a].read_noise * g1);
-    ivec2 o;
-    o.x = (int32_t)v0; o.y = (int32_t)v1;
-    *(ivec2*)(out + p) = o;
-}
-
-__global__ __launch_bounds__(256) void k_readout_finish(const float* __restrict__ seg, const ims_readout_t ro, uint64_t seed,
-                                                        int32_t* __restrict__ out)
-{
-    const int64_t per = (int64_t)ro.raw_w * ro.raw_h;
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= per * ro.n_amps) return;
-    const int a = (int)(p / per);
-    const int64_t q = p - (int64_t)a * per;
-    float v = seg[p] + ro.amps[a].bias_level;
-    Rng r;
-    rng_reset(r);
-    rng_block(r, seed, READOUT_ID_BASE + a, q >> 1, 0u);
-    double g0, g1;
-    gauss_words(r.w[0], r.w[1], g0, g1);
-    v = v + (float)((double)ro.amps[a].read_noise * ((q & 1) ? g1 : g0));
-    out[p] = (int32_t)v;
-}
-
-// ---------------- phase-screen pre-pass (include/imsim_hip.h: ims_screen_prepass) ----------------
-struct ScreenSlices { int64_t first[9]; int64_t seg_first[9]; };     // first object / first segment of every slice
-constexpr int SCR_MAXB = 256;
-constexpr int SCR_CH = 16;            // segments (of 256 photons) one workgroup of the sort kernels works through
-
-// MODE 0: count the photons of every (slice, time bucket); MODE 1: scatter (object, photon index) into slice-major, time-minor
-// order (bins = the exclusive prefix of the counts; the order inside a bin is that of the atomics and does not matter).
-// Block b works on slice b mod 8, on SCR_CH consecutive segments of it: its 4 096 photons are counted in LDS first, so a bin
-// costs ONE global atomic per workgroup (one per 256-photon segment was 75 M atomics on 1 024 counters: 4 ms), and the
-// entries a workgroup adds to a bin are neighbours in memory.
-template <int MODE>
-__global__ __launch_bounds__(256) void k_screen_sort(const ims_render_params_t P, int comp, int n_buckets, const ScreenSlices S,
-                                                     unsigned long long* __restrict__ bins, int64_t* __restrict__ entries)
-{
-    __shared__ unsigned int hist[SCR_MAXB];
-    __shared__ unsigned long long base[SCR_MAXB];
-    const int x = blockIdx.x & 7;
-    const int64_t seg0 = S.seg_first[x] + (int64_t)(blockIdx.x >> 3) * SCR_CH;
-    const int64_t seg_end = S.seg_first[x + 1];
-    if (seg0 >= seg_end) return;
-    if ((int)threadIdx.x < n_buckets) hist[threadIdx.x] = 0u;
-    __syncthreads();
-    unsigned char bucket[SCR_CH];
-    unsigned int valid = 0u;
-#pragma unroll
-    for (int c = 0; c < SCR_CH; ++c) {
-        const int64_t seg = seg0 + c;
-        bucket[c] = 0;
-        if (seg >= seg_end) continue;
-        const int64_t oi = P.seg_object ? (int64_t)P.seg_object[seg] : find_object(P.seg_prefix, P.n_objects, seg);
-        const ims_object_t& o = P.objects[oi];
-        const int64_t j = (seg - P.seg_prefix[oi]) * P.seg_size + threadIdx.x;
-        if (j >= o.n_phot) continue;
-        Rng rng;
-        rng_reset(rng);
-        rng_block(rng, P.seed, o.obj_id, o.phot_first + j, SLOT_PSF_TIME + (uint32_t)comp);
-        const int bk = (int)(((unsigned long long)rng.w[0] * (unsigned long long)n_buckets) >> 32);   // floor(u n): monotone in the time
-        bucket[c] = (unsigned char)bk;
-        valid |= 1u << c;
-        atomicAdd(&hist[bk], 1u);
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < n_buckets) {
-        const unsigned int cnt = hist[threadIdx.x];
-        if (cnt != 0u) {
-            const unsigned long long got = atomicAdd(&bins[x * n_buckets + threadIdx.x], (unsigned long long)cnt);
-            if (MODE == 1) base[threadIdx.x] = got;
-        }
-        if (MODE == 1) hist[threadIdx.x] = 0u;           // becomes the cursor inside the workgroup's share of the bin
-    }
-    if (MODE == 1) {
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < SCR_CH; ++c) {
-            if (!(valid & (1u << c))) continue;
-            const int64_t seg = seg0 + c;
-            const int64_t oi = P.seg_object ? (int64_t)P.seg_object[seg] : find_object(P.seg_prefix, P.n_objects, seg);
-            const ims_object_t& o = P.objects[oi];
-            const int64_t k = o.phot_first + (seg - P.seg_prefix[oi]) * P.seg_size + threadIdx.x;
-            const unsigned int rank = atomicAdd(&hist[bucket[c]], 1u);
-            entries[base[bucket[c]] + rank] = (int64_t)(((unsigned long long)oi << 32) | (unsigned long long)(uint32_t)k);
-        }
-    }
-}
-
-// exclusive prefix of the counts in place (slice-major, bucket-minor) + the slice boundaries behind them
-__global__ void k_screen_scan(unsigned long long* __restrict__ bins, int n_bins, int n_buckets)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    unsigned long long run = 0ull;
-    for (int i = 0; i < n_bins; ++i) {
-        if (i % n_buckets == 0) bins[n_bins + i / n_buckets] = run;          // start of slice i / n_buckets
-        const unsigned long long c = bins[i];
-        bins[i] = run;
-        run += c;
-    }
-    bins[n_bins + 8] = run;
-}
-
-// what the gather needs of an object, 32 bytes instead of a 256-byte row (3 MB for 100 000 objects: the rows of a slice would
-// take as much of the XCD's L2 as the screen windows the pre-pass is there to keep)
-struct ScreenObject { int64_t obj_id, screen_base; double tan_x, tan_y; };
-
-__global__ __launch_bounds__(256) void k_screen_objects(const ims_render_params_t P, ScreenObject* __restrict__ slim)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= P.n_objects) return;
-    const ims_object_t& o = P.objects[i];
-    ScreenObject q = { o.obj_id, o.screen_base, o.atm_tan_x, o.atm_tan_y };
-    slim[i] = q;
-}
-
-// Slice x in time order on XCD x: block b works on the x = b mod 8 slice, chunk b / 8.  The entries stream in and the kicks
-// stream out past the cache (non-temporal): what stays in the XCD's L2 are the screen windows and the 32-byte object records.
-__global__ __launch_bounds__(256) void k_screen_gather(const ims_render_params_t P, int comp, const unsigned long long* __restrict__ slice_start,
-                                                       const int64_t* __restrict__ entries, const ScreenObject* __restrict__ slim,
-                                                       double* __restrict__ kick)
-{
-    const int x = blockIdx.x & 7;
-    const unsigned long long pos = slice_start[x] + (unsigned long long)(blockIdx.x >> 3) * 256ull + threadIdx.x;
-    if (pos >= slice_start[x + 1]) return;
-    const unsigned long long e = (unsigned long long)__builtin_nontemporal_load(entries + pos);
-    const int64_t oi = (int64_t)(e >> 32), k = (int64_t)(e & 0xFFFFFFFFull);
-    const ScreenObject o = slim[oi];
-    const ims_atmosphere_t& A = *P.atm;
-    Rng rng;
-    rng_reset(rng);
-    rng_block(rng, P.seed, o.obj_id, k, SLOT_PSF + ((uint32_t)comp >> 1));
-    const uint32_t wa = (comp & 1) ? rng.w[2] : rng.w[0], wb = (comp & 1) ? rng.w[3] : rng.w[1];
-    const double r = dsqrt0(A.aper_ri2 + w01(wa) * A.aper_dr2);
-    double s, cc;
-    sincos2pi_w(wb, s, cc);
-    const double pu = r * cc, pv = r * s;
-    rng_block(rng, P.seed, o.obj_id, k, SLOT_PSF_TIME + (uint32_t)comp);
-    const double t = A.t0 + w01(rng.w[0]) * A.exptime;
-    double gx, gy;
-    screen_gradient<true>(A, pu, pv, t, o.tan_x, o.tan_y, gx, gy);
-    double* dst = kick + 2 * (o.screen_base + k);
-    __builtin_nontemporal_store(gx, dst);
-    __builtin_nontemporal_store(gy, dst + 1);
-}
-
 // ---------------- object table on the device (include/imsim_hip.h: ims_build_object_table) ----------------
 // One thread per catalog source.  The test-side CPU restatement repeats this arithmetic; the formulas are those of
 // imsim_amd/catalog.py (the numpy builder, which stays the portable host path).
@@ -4724,225 +4379,11 @@ int ims_object_spectra(const double* grid, const double* thr, const double* ext_
     return IMS_OK;
 }
 
-// Launch-wide constants of the air index (host arithmetic, IEEE binary64, same operation order as the
-// oracle's restatement): n - 1 = air_p * dispersion(wavelength) - air_w * water(wavelength).
-static void air_factors(double p_kpa, double t_k, double h2o_kpa, double* air_p, double* air_w)
-{
-    const double Pm = p_kpa * 7.50061683;
-    const double T = t_k - 273.15;
-    const double W = h2o_kpa * 7.50061683;
-    const double tf = 1.0 + 0.003661 * T;
-    *air_p = 1.0e-6 * (Pm * (1.0 + (1.049 - 0.0157 * T) * 1.0e-6 * Pm) / (720.883 * tf));
-    *air_w = W * 1.0e-6 / tf;
-}
-static double host_air_n_minus_one(double wave_nm, double air_p, double air_w)
-{
-    const double wm = wave_nm * 1.0e-3;
-    const double w2 = wm * wm;
-    const double d1 = fma(146.0, w2, -1.0), d2 = fma(41.0, w2, -1.0);
-    const double den = d1 * d2;
-    const double num = fma(29498.1, d2, 255.4 * d1);
-    const double disp = fma(64.328, den, w2 * num);
-    const double wat = fma(0.0624, w2, -0.000680) * den;
-    return (air_p * (disp * w2) - air_w * wat) / (den * w2);
-}
-
-int ims_fill_derived_op(ims_op_t* op)
-{
-    if (!op) return set_err(IMS_ERR_ARG, "op is NULL");
-    if (op->kind == IMS_OP_PHOTON_DCR) {
-        air_factors(op->p[1], op->p[2], op->p[3], &op->p[5], &op->p[6]);
-        const double nm1 = host_air_n_minus_one(op->p[0], op->p[5], op->p[6]);
-        op->p[7] = nm1 * (nm1 + 2.0) / 2.0 / (nm1 * nm1 + 2.0 * nm1 + 1.0);
-    }
-    if (op->kind == IMS_OP_PUPIL_ANNULUS_SAMPLER) {
-        const double ro2 = op->p[0] * op->p[0], ri2 = op->p[1] * op->p[1];
-        op->p[2] = ri2; op->p[3] = ro2 - ri2;
-    }
-    if (op->kind == IMS_OP_REFRACTION) {
-        const double nn = op->p[0] * op->p[0];
-        op->p[1] = nn; op->p[2] = nn - 1.0;
-    }
-    return IMS_OK;
-}
-
-// The derived constants below are single IEEE operations (this file is compiled with -ffp-contract=off), so the kernels
-// compute with exactly the values they would have formed themselves.
-int ims_fill_derived_optics(ims_optics_t* o)
-{
-    if (!o) return set_err(IMS_ERR_ARG, "optics is NULL");
-    if (o->n_surfaces < 0 || o->n_surfaces > IMS_MAX_SURFACES) return set_err(IMS_ERR_ARG, "n_surfaces out of range");
-    for (int k = 0; k < o->n_surfaces; ++k) {
-        ims_surface_t& S = o->surf[k];
-        S.k1 = 1.0 + S.conic;
-        S.k1c = S.k1 * S.inv_R;
-        S.m2R = -2.0 * S.R;
-        S.cc = S.inv_R * S.inv_R;
-        S.obsc_i2 = S.obsc_inner * S.obsc_inner;
-        S.obsc_o2 = S.obsc_outer * S.obsc_outer;
-        for (int a = 0; a < 4; ++a) S.asph_d[a] = S.asph[a] * (double)(a + 2);
-    }
-    const double* ef = o->e_focal;
-    const double* z0 = o->e_z0;
-    o->rot_g[0] = ef[1] * z0[2] - ef[2] * z0[1];
-    o->rot_g[1] = ef[2] * z0[0] - ef[0] * z0[2];
-    o->rot_g[2] = ef[0] * z0[1] - ef[1] * z0[0];
-    o->rot_gnorm = sqrt(o->rot_g[0] * o->rot_g[0] + o->rot_g[1] * o->rot_g[1] + o->rot_g[2] * o->rot_g[2]);
-    return IMS_OK;
-}
-
-int ims_fill_derived_atmosphere(ims_atmosphere_t* A)
-{
-    if (!A) return set_err(IMS_ERR_ARG, "atmosphere is NULL");
-    if (A->npix <= 0 || !(A->scale > 0.0)) return set_err(IMS_ERR_ARG, "atmosphere: npix and scale must be positive");
-    A->dn = (double)A->npix;
-    A->inv_n = 1.0 / A->dn;
-    A->inv_scale = 1.0 / A->scale;
-    const double ro2 = A->aper_r_outer * A->aper_r_outer, ri2 = A->aper_r_inner * A->aper_r_inner;
-    A->aper_ri2 = ri2;
-    A->aper_dr2 = ro2 - ri2;
-    return IMS_OK;
-}
-
-int ims_fill_derived_sensor(ims_sensor_t* S)
-{
-    if (!S) return set_err(IMS_ERR_ARG, "sensor is NULL");
-    if (S->kind == IMS_SENSOR_SILICON) {
-        if (!(S->thickness > 0.0) || !(S->pixel_size > 0.0)) return set_err(IMS_ERR_ARG, "sensor: thickness and pixel_size must be positive");
-        S->diff_coef = S->diff_step / (S->thickness * S->pixel_size);
-        S->thick_m1 = S->thickness - 1.0;
-    }
-    return IMS_OK;
-}
-
-int ims_fill_derived_medium(int32_t kind, double* c6)
-{
-    if (!c6) return set_err(IMS_ERR_ARG, "c6 is NULL");
-    if (kind == IMS_MEDIUM_AIR) air_factors(c6[0], c6[1], c6[2], &c6[3], &c6[4]);
-    return IMS_OK;
-}
-
 int ims_image_to_float(const double* src, float* dst, int64_t n, void* stream)
 {
     if (!dst || !src) return set_err(IMS_ERR_ARG, "dst/src is NULL");
     if (n <= 0) return IMS_OK;
     hipLaunchKernelGGL(k_image_to_float, dim3(grid_for_pool(n)), dim3(256), 0, (hipStream_t)stream, src, dst, n);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-static int check_readout(const ims_readout_t* ro)
-{
-    if (!ro) return set_err(IMS_ERR_ARG, "readout descriptor is NULL");
-    if (ro->n_amps < 1 || ro->n_amps > IMS_MAX_AMPS) return set_err(IMS_ERR_ARG, "n_amps out of range");
-    if (ro->seg_w < 1 || ro->seg_h < 1 || ro->data_x0 < 0 || ro->data_y0 < 0 || ro->data_x0 + ro->seg_w > ro->raw_w ||
-        ro->data_y0 + ro->seg_h > ro->raw_h)
-        return set_err(IMS_ERR_ARG, "imaging section does not fit the raw segment");
-    for (int a = 0; a < ro->n_amps; ++a)
-        if (!(ro->amps[a].gain > 0.0f)) return set_err(IMS_ERR_ARG, "amplifier gain must be positive");
-    return IMS_OK;
-}
-
-int ims_readout_bleed(double* image_dev, unsigned char* flags_dev, int32_t nx, int32_t ny, double full_well,
-                      int32_t midline_stop, void* stream)
-{
-    if (!image_dev || !flags_dev) return set_err(IMS_ERR_ARG, "image / flags is NULL");
-    if (nx < 1 || ny < 1) return set_err(IMS_ERR_ARG, "empty image");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t n = (int64_t)nx * ny;
-    int* span = (int*)(flags_dev + ((n + 15) / 16) * 16);        // the tail of the scratch: 4 ints per column
-    hipLaunchKernelGGL(k_readout_span_init, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, st, span, nx);
-    hipLaunchKernelGGL(k_readout_flags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, image_dev, flags_dev, span, nx, ny,
-                       full_well, midline_stop ? 1 : 0);
-    const int threads = nx * (midline_stop ? 2 : 1);
-    hipLaunchKernelGGL(k_readout_bleed, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, image_dev, flags_dev, span, nx, ny,
-                       full_well, midline_stop ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_readout_segments(const double* image_dev, int32_t nx, int32_t ny, const ims_readout_t* ro, float* seg_dev, void* stream)
-{
-    if (int e = check_readout(ro)) return e;
-    if (!image_dev || !seg_dev) return set_err(IMS_ERR_ARG, "image / segments is NULL");
-    for (int a = 0; a < ro->n_amps; ++a)
-        if (ro->amps[a].x0 < 0 || ro->amps[a].y0 < 0 || ro->amps[a].x0 + ro->seg_w > nx || ro->amps[a].y0 + ro->seg_h > ny)
-            return set_err(IMS_ERR_ARG, "amplifier section outside the e-image");
-    hipLaunchKernelGGL(k_readout_segments, dim3((unsigned)((ro->raw_w + 63) / 64), (unsigned)((ro->raw_h + 3) / 4), 1u),
-                       dim3(64, 4), 0, (hipStream_t)stream, image_dev, nx, *ro, seg_dev);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_readout_cte(const float* src_dev, float* dst_dev, const ims_readout_t* ro, const double* band_dev, int32_t n_band,
-                    int32_t axis, void* stream)
-{
-    if (int e = check_readout(ro)) return e;
-    if (!src_dev || !dst_dev || !band_dev) return set_err(IMS_ERR_ARG, "src / dst / band is NULL");
-    if (src_dev == dst_dev) return set_err(IMS_ERR_ARG, "ims_readout_cte is out of place: src and dst must differ");
-    if (n_band < 1 || (axis != 0 && axis != 1)) return set_err(IMS_ERR_ARG, "n_band / axis out of range");
-    if ((int64_t)ro->raw_w * ro->raw_h * ro->n_amps >= (1ll << 31)) return set_err(IMS_ERR_ARG, "raw segments too large");
-    const dim3 grid((unsigned)((ro->raw_w + 63) / 64), (unsigned)((ro->raw_h + 3) / 4), (unsigned)ro->n_amps);
-    if (n_band == 21)
-        hipLaunchKernelGGL(k_readout_cte<21>, grid, dim3(64, 4), 0, (hipStream_t)stream, src_dev, dst_dev, ro->raw_w, ro->raw_h,
-                           band_dev, n_band, axis);
-    else
-        hipLaunchKernelGGL(k_readout_cte<0>, grid, dim3(64, 4), 0, (hipStream_t)stream, src_dev, dst_dev, ro->raw_w, ro->raw_h,
-                           band_dev, n_band, axis);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_readout_finish(const float* seg_dev, const ims_readout_t* ro, uint64_t seed, int32_t* out_dev, void* stream)
-{
-    if (int e = check_readout(ro)) return e;
-    if (!seg_dev || !out_dev) return set_err(IMS_ERR_ARG, "segments / output is NULL");
-    const int64_t n = (int64_t)ro->raw_w * ro->raw_h * ro->n_amps;
-    if ((((int64_t)ro->raw_w * ro->raw_h) & 1) == 0 && (((uintptr_t)seg_dev | (uintptr_t)out_dev) & 7u) == 0)
-        hipLaunchKernelGGL(k_readout_finish_pairs, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seg_dev, *ro,
-                           seed, out_dev);
-    else
-        hipLaunchKernelGGL(k_readout_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seg_dev, *ro, seed,
-                           out_dev);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_screen_prepass(const ims_render_params_t* params, int32_t comp, int32_t n_buckets, const int64_t* slice_first_host,
-                       int64_t max_slice_photons, int64_t* scratch_dev, int64_t* entries_dev, double* kick_dev, void* stream)
-{
-    if (!params || !slice_first_host || !scratch_dev || !entries_dev || !kick_dev) return set_err(IMS_ERR_ARG, "NULL argument");
-    if (!params->objects || !params->seg_prefix || !params->atm) return set_err(IMS_ERR_ARG, "objects / seg_prefix / atm is NULL");
-    if (comp < 0 || comp >= params->n_psf || params->psf[comp].kind != IMS_PSF_SCREENS)
-        return set_err(IMS_ERR_ARG, "comp is not a phase-screen PSF component");
-    if (n_buckets < 1 || n_buckets > SCR_MAXB || (n_buckets & (n_buckets - 1)) != 0) return set_err(IMS_ERR_ARG, "n_buckets must be a power of two <= 256");
-    if (params->seg_size != 256) return set_err(IMS_ERR_ARG, "seg_size must be 256");
-    if (params->n_segments <= 0) return IMS_OK;
-    if (params->n_segments > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "too many segments");
-    ScreenSlices S;
-    int64_t max_segs = 0;
-    for (int q = 0; q < 9; ++q) {
-        S.first[q] = slice_first_host[q];
-        S.seg_first[q] = slice_first_host[9 + q];
-        if (q > 0 && S.seg_first[q] - S.seg_first[q - 1] > max_segs) max_segs = S.seg_first[q] - S.seg_first[q - 1];
-    }
-    if (S.seg_first[0] != 0 || S.seg_first[8] != params->n_segments) return set_err(IMS_ERR_ARG, "slice segment boundaries do not cover the table");
-    // (every argument is checked before the first launch: a refused call leaves nothing enqueued)
-    if (max_slice_photons <= 0 || (max_slice_photons + 255) / 256 * 8 > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "max_slice_photons out of range");
-    hipStream_t st = (hipStream_t)stream;
-    const int n_bins = 8 * n_buckets;
-    unsigned long long* bins = (unsigned long long*)scratch_dev;
-    HIP_TRY(hipMemsetAsync(bins, 0, sizeof(unsigned long long) * (size_t)(n_bins + 16), st));
-    const dim3 grid((unsigned)(8 * ((max_segs + SCR_CH - 1) / SCR_CH)));
-    hipLaunchKernelGGL(k_screen_sort<0>, grid, dim3(256), 0, st, *params, comp, n_buckets, S, bins, (int64_t*)nullptr);
-    hipLaunchKernelGGL(k_screen_scan, dim3(1), dim3(64), 0, st, bins, n_bins, n_buckets);
-    hipLaunchKernelGGL(k_screen_sort<1>, grid, dim3(256), 0, st, *params, comp, n_buckets, S, bins, entries_dev);
-    // every slice gets the blocks of the largest one (a block beyond its slice's end leaves at once); the slice boundaries sit
-    // behind the bins, whose cursors the scatter has advanced to the bin ends
-    ScreenObject* slim = (ScreenObject*)(scratch_dev + n_bins + 16);
-    hipLaunchKernelGGL(k_screen_objects, dim3((unsigned)((params->n_objects + 255) / 256)), dim3(256), 0, st, *params, slim);
-    hipLaunchKernelGGL(k_screen_gather, dim3((unsigned)(8 * ((max_slice_photons + 255) / 256))), dim3(256), 0, st,
-                       *params, comp, bins + n_bins, entries_dev, slim, kick_dev);
     HIP_TRY(hipGetLastError());
     return IMS_OK;
 }
@@ -4986,116 +4427,6 @@ int ims_gather_rows(const ims_object_t* rows_dev, const int64_t* index_dev, cons
                        count_dev, bf_state_dev, clear_flags, dst_dev, n);
     HIP_TRY(hipGetLastError());
     return IMS_OK;
-}
-
-// ---- instance-catalog tokenizer: plain host code (the catalog reader is per-line Python in the reference) ----
-static bool tok_double(const char* p, int len, double* out)
-{
-    char buf[64];
-    if (len <= 0 || len >= (int)sizeof(buf)) return false;
-    memcpy(buf, p, len);
-    buf[len] = 0;
-    char* end = nullptr;
-    *out = strtod(buf, &end);
-    return end == buf + len;
-}
-static bool tok_is(const char* p, int len, const char* word)
-{
-    const int n = (int)strlen(word);
-    if (len != n) return false;
-    for (int i = 0; i < n; ++i) {
-        char c = p[i];
-        if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a');
-        if (c != word[i]) return false;
-    }
-    return true;
-}
-static bool tok_ends(const char* p, int len, const char* suffix)
-{
-    const int n = (int)strlen(suffix);
-    return len >= n && memcmp(p + len - n, suffix, n) == 0;
-}
-
-int64_t ims_parse_instcat_objects(const char* text, int64_t n_bytes, int64_t max_objects, double* num, int32_t* kind, int64_t* span)
-{
-    if (!text || !num || !kind || !span || n_bytes < 0 || max_objects < 0) { set_err(IMS_ERR_ARG, "NULL argument"); return -1; }
-    constexpr int MAXT = 32;
-    int64_t n_out = 0, n_line = 0;
-    int64_t pos = 0;
-    while (pos < n_bytes && n_out < max_objects) {
-        int64_t eol = pos;
-        while (eol < n_bytes && text[eol] != '\n') ++eol;
-        const char* ln = text + pos;
-        const int64_t len = eol - pos;
-        pos = eol + 1;
-        if (len < 6 || memcmp(ln, "object", 6) != 0) continue;
-        const int64_t this_line = n_line++;
-        bool has_inf = false;
-        for (int64_t i = 0; i + 5 <= len; ++i)
-            if (ln[i] == ' ' && ln[i + 1] == 'i' && ln[i + 2] == 'n' && ln[i + 3] == 'f' && ln[i + 4] == ' ') { has_inf = true; break; }
-        if (has_inf) continue;
-        const char* tp[MAXT]; int tl[MAXT]; int nt = 0;
-        for (int64_t i = 0; i < len && nt < MAXT;) {
-            while (i < len && (ln[i] == ' ' || ln[i] == '\t' || ln[i] == '\r' || ln[i] == '\v' || ln[i] == '\f')) ++i;
-            if (i >= len) break;
-            const int64_t a = i;
-            while (i < len && !(ln[i] == ' ' || ln[i] == '\t' || ln[i] == '\r' || ln[i] == '\v' || ln[i] == '\f')) ++i;
-            tp[nt] = ln + a; tl[nt] = (int)(i - a); ++nt;
-        }
-        if (nt < 13) return -(this_line + 1);
-        double v[16] = { 0.0 };
-        int k = 5, di = 15;
-        double a = 0.0, b = 0.0, pa = 0.0, nn = 0.0;
-        auto need = [&](int t, double* out) { return t < nt && tok_double(tp[t], tl[t], out); };
-        if (!need(4, &v[2])) return -(this_line + 1);
-        if (tok_is(tp[12], tl[12], "point")) { k = 0; di = 13; }
-        else if (tok_is(tp[12], tl[12], "sersic2d")) {
-            k = 1; di = 17;
-            double raw;
-            if (!need(13, &a) || !need(14, &b) || !need(15, &pa) || !need(16, &raw)) return -(this_line + 1);
-            nn = nearbyint(raw * 20.0) / 20.0;                    // Python's round(): half to even, as nearbyint in the default mode
-        } else if (tok_is(tp[12], tl[12], "knots")) {
-            k = 2; di = 17;
-            if (!need(13, &a) || !need(14, &b) || !need(15, &pa)) return -(this_line + 1);
-            // int(token): a decimal integer literal only
-            if (16 >= nt) return -(this_line + 1);
-            char buf[32];
-            if (tl[16] <= 0 || tl[16] >= (int)sizeof(buf)) return -(this_line + 1);
-            memcpy(buf, tp[16], tl[16]); buf[tl[16]] = 0;
-            char* end = nullptr;
-            const long long iv = strtoll(buf, &end, 10);
-            if (end != buf + tl[16]) return -(this_line + 1);
-            nn = (double)iv;
-        } else if (tok_is(tp[12], tl[12], "streak")) {
-            k = 3; di = 16;
-            if (!need(13, &a) || !need(14, &b) || !need(15, &pa)) return -(this_line + 1);
-        } else if (tok_ends(tp[12], tl[12], ".fits") || tok_ends(tp[12], tl[12], ".fits.gz")) {
-            k = 4;
-            if (!need(13, &a) || !need(14, &pa)) return -(this_line + 1);
-        }
-        const bool valid = v[2] < 50.0 && !((k == 1 || k == 2) && a < b) && !(k == 2 && nn <= 0.0);
-        if (!valid) continue;
-        if (!need(2, &v[0]) || !need(3, &v[1]) || !need(6, &v[3]) || !need(7, &v[4]) || !need(8, &v[5]) || !need(9, &v[6]))
-            return -(this_line + 1);
-        v[7] = a; v[8] = b; v[9] = pa; v[10] = nn;
-        v[11] = 0.0; v[12] = 3.1; v[13] = 0.0; v[14] = 3.1;
-        int d = di;
-        if (d < nt && !tok_is(tp[d], tl[d], "none")) {
-            if (!need(d + 1, &v[11]) || !need(d + 2, &v[12])) return -(this_line + 1);
-            d += 3;
-        } else d += 1;
-        if (d < nt && !tok_is(tp[d], tl[d], "none")) {
-            if (!need(d + 1, &v[13]) || !need(d + 2, &v[14])) return -(this_line + 1);
-        }
-        memcpy(num + n_out * 16, v, sizeof(v));
-        kind[n_out] = k;
-        int64_t* sp = span + n_out * 6;
-        sp[0] = tp[1] - text; sp[1] = tl[1];
-        sp[2] = tp[5] - text; sp[3] = tl[5];
-        sp[4] = tp[12] - text; sp[5] = tl[12];
-        ++n_out;
-    }
-    return n_out;
 }
 
 static int opd_run(const ims_opd_t* P, const ims_optics_t* optics_dev, bool pert, void* stream)
@@ -5181,6 +4512,10 @@ int ims_trace_field_points_perturbed(const ims_optics_perturbed_t* optics_dev, c
 
 }  // extern "C"
 
+#include "ims_readout.h"        // CCD readout: bleed trails, amplifier segments, CTE, noise and digitisation
+#include "ims_screen.h"         // phase-screen pre-pass
+#include "ims_derive.h"         // derived constants of the descriptors (host only)
+#include "ims_instcat.h"        // instance-catalog tokenizer (host only)
 #include "ims_knots.h"          // RandomKnots on the FFT branch: knot positions and the structure-factor pass
 #include "ims_stamp_fft.h"      // FITS stamps on the FFT branch: the pixel spectrum times the interpolant's transform
 #include "ims_profile.h"        // radial / azimuthal histograms of the delivered PSF (the photons of ims_psf_moments, binned)

@@ -302,3 +302,41 @@ def test_the_dpp_hazard_check_follows_labels_and_branches(tmp_path):
     assert n == 1 and len(bad) == 1 and "2 wait states" in bad[0][4]
     assert len(run(jump.replace("\ts_cbranch_vccnz", "\ts_nop 0\n\ts_cbranch_vccnz"))[1]) == 0
     assert len(run("\tv_cmpx_gt_u32 v1, v0\n\ts_nop 2\n.LBB0_1:\n\tv_fmac_f64_dpp v[4:5], v[2:3], v[6:7] row_newbcast:1\n")[1]) == 1
+
+
+def test_the_device_code_comparison_ignores_order_and_reports_changes(tmp_path):
+    """tools/device_code_diff.py on hand-made assembly: two files that differ in the order of their functions, the ordinals of
+    their labels and the order of the metadata records are the same code; a changed instruction is reported with its function,
+    a missing kernel with its name, a changed .vgpr_count with its record."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import device_code_diff
+
+    def function(name, ordinal, op="v_add_f64 v[0:1], v[0:1], v[2:3]"):
+        return (f"\t.protected\t{name} ; -- Begin function {name}\n\t.globl\t{name}\n\t.type\t{name},@function\n{name}: ; @{name}\n"
+                f"; %bb.0:\n\ts_cbranch_scc1 .LBB{ordinal}_2\n.Ltmp{7 * ordinal + 3}:\n\t{op}\n.LBB{ordinal}_2: ; a comment\n\ts_endpgm\n"
+                f"\t.amdhsa_kernel {name}\n\t\t.amdhsa_next_free_vgpr 4\n\t.end_amdhsa_kernel\n.Lfunc_end{ordinal}:\n"
+                f"\t.size\t{name}, .Lfunc_end{ordinal}-{name}\n\t.set {name}.num_vgpr, 4\n; NumVgprs: 4\n")
+
+    def record(name, vgprs=4):
+        return f"  - .args:\n      - .offset:         0\n        .size:           8\n    .name:           {name}\n    .vgpr_count:     {vgprs}\n"
+
+    def write(tag, functions, records, cuid):
+        f = tmp_path / f"{tag}.s"
+        f.write_text("\t.text\n" + "".join(functions) + f"\t.type\t__hip_cuid_{cuid},@object\n__hip_cuid_{cuid}:\n\t.byte\t0\n"
+                     f"\t.size\t__hip_cuid_{cuid}, 1\n\t.amdgpu_metadata\n---\namdhsa.kernels:\n" + "".join(records) +
+                     "amdhsa.target:   amdgcn-amd-amdhsa--gfx950\namdhsa.version:\n  - 1\n  - 2\n...\n\n\t.end_amdgpu_metadata\n")
+        return str(f)
+    a = write("a", [function("k_one", 0), function("k_two", 1)], [record("k_one"), record("k_two")], "1a2b")
+    moved = write("moved", [function("k_two", 0), function("k_one", 1)], [record("k_two"), record("k_one")], "3c4d")
+    assert device_code_diff.compare(a, moved) == []
+    changed = write("changed", [function("k_two", 0, "v_mul_f64 v[0:1], v[0:1], v[2:3]"), function("k_one", 1)],
+                    [record("k_two"), record("k_one")], "3c4d")
+    assert [(kind, name) for kind, name, _ in device_code_diff.compare(a, changed)] == [("text", "k_two")]
+    assert "v_mul_f64" in device_code_diff.compare(a, changed)[0][2]
+    missing = write("missing", [function("k_one", 0)], [record("k_one")], "3c4d")
+    assert {(kind, name) for kind, name, _ in device_code_diff.compare(a, missing)} >= {("only_in_a", "k_two"), ("kernel_only_in_a", "k_two")}
+    assert ("only_in_b", "k_two") in {(kind, name) for kind, name, _ in device_code_diff.compare(missing, a)}
+    fatter = write("fatter", [function("k_one", 0), function("k_two", 1)], [record("k_one"), record("k_two", 6)], "1a2b")
+    found = device_code_diff.compare(a, fatter)
+    assert [(kind, name) for kind, name, _ in found] == [("kernel_record", "k_two")] and ".vgpr_count:     4 -> .vgpr_count:     6" in found[0][2]
