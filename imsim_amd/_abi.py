@@ -351,7 +351,7 @@ EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_
            "ims_count_inexact", "ims_struct_size", "ims_test_math", "ims_opd", "ims_opd_perturbed",
            "ims_paint_cosmic_rays", "ims_test_optical_screen", "ims_trace_field_points", "ims_trace_field_points_perturbed",
            "ims_object_spectra", "ims_psf_moments", "ims_knot_positions", "ims_fft_knots_factor",
-           "ims_fft_image_factor", "ims_psf_profile"]
+           "ims_fft_image_factor", "ims_psf_profile", "ims_psf_adaptive"]
 
 _LIB_PATH = tuning.env("IMSIM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libimsim_hip.so")
 _lib = None
@@ -467,6 +467,7 @@ def load():
     lib.ims_trace_field_points_perturbed.argtypes = [c_vp, c_vp, c_vp, c_i64, c_d, c_vp, c_i32, c_vp, c_vp, c_vp]
     lib.ims_psf_moments.argtypes = [C.POINTER(RenderParams), c_i32, c_vp, c_vp, c_vp, c_vp]
     lib.ims_psf_profile.argtypes = [C.POINTER(RenderParams), c_i32, C.POINTER(PsfProfile), c_vp, c_vp, c_vp, c_vp]
+    lib.ims_psf_adaptive.argtypes = [C.POINTER(RenderParams), c_i32, c_i32, c_d, c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.ims_object_spectra.argtypes = [c_vp, c_vp, c_vp, c_vp, c_i32, c_d, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,
                                        c_i32, c_vp, c_vp, c_i64, c_vp]
     _lib = lib

@@ -1177,6 +1177,33 @@ typedef struct ims_psf_profile {
 int  ims_psf_profile(const ims_render_params_t* params, int32_t stage, const ims_psf_profile_t* spec, const double* centre_dev,
                      int64_t* counts_dev, int64_t* dropped_dev, void* stream);
 
+/* ---- adaptive moments of the delivered PSF at a table of field points, iterated on the device ----
+ * The rows, the stages and the photons are those of ims_psf_moments: photon k of a row is the same photon, bit for bit, and
+ * (dx, dy) the same offset.  Per row the call iterates an elliptical Gaussian weight towards the profile (Bernstein & Jarvis 2002;
+ * Hirata & Seljak 2003): n_rounds times a pass that shoots the row's photons again and reduces them under the current weight, and an
+ * update of the weight by one thread.  Nothing is synchronised and nothing is read back: the caller looks at status_dev when it
+ * likes and calls again to go on; rounds delivered as 16 or as 4 x 4 give the same bits.
+ *   state_dev [n][5]   in/out  x0, y0, Mxx, Mxy, Myy: the weight's centre and matrix, in the stage's units (the caller's start)
+ *   status_dev [n][2]  in/out  status, iter (int32).  0 converged, 1 running, 2 failed, 3 no photon arrived.  Only rows that enter
+ *                              with status 1 are worked on; the workgroups of every other row return before shooting a photon.
+ *   aux_dev [n][4]     out     rho4 = R / A of the row's last completed update, sum w, photons used, photons dropped (the counts as
+ *                              f64 integers); written for rows that are worked on, left alone otherwise
+ *   partial_dev                device scratch of 10 * n_segments doubles, overwritten: per 256-photon segment the seven weighted
+ *                              sums below, sum w (which aux_dev reports) and the two counts
+ * Pass, for every photon with w = flux != 0 (the others are counted as dropped):
+ *   u = dx - x0, v = dy - y0, det = Mxx Myy - Mxy^2, rho2 = (Myy u u - 2 Mxy u v + Mxx v v) / det, g = w exp(-rho2 / 2)
+ *   A = sum g; Bx = sum g u, By = sum g v; Cxx = sum g u u, Cxy = sum g u v, Cyy = sum g v v; R = sum g rho2^2
+ * in ims_psf_moments' fixed order of additions, without atomics.  Update, one f64 evaluation per row in this order:
+ *   T = Mxx + Myy, D = sqrt((Mxx - Myy)^2 + 4 Mxy^2), a2 = (T + D) / 2, b2 = (T - D) / 2, s = sqrt(b2)
+ *   ex = 2 Bx / (A s), ey = 2 By / (A s), exx = 4 (Cxx / A - Mxx / 2) / b2, exy and eyy likewise; each clipped to [-1/4, 1/4]
+ *   conv = max |e.| sqrt(a2 / b2);  x0 += ex s, y0 += ey s, Mxx += exx b2, Mxy += exy b2, Myy += eyy b2;  iter += 1
+ * conv < tol: status 0, the row is frozen.  A not finite or <= 0, or the new matrix not finite or not positive definite (Mxx <= 0
+ * or det <= 0): status 2, the state stays at its last valid values (iter is not advanced), frozen.  No photon arrived: status 3,
+ * the state is NaN.  A row's result depends on nothing but the row.  Added in ABI version 22 without changing any existing struct
+ * or function, so the version number stays. */
+int  ims_psf_adaptive(const ims_render_params_t* params, int32_t stage, int32_t n_rounds, double tol, double* partial_dev,
+                      double* state_dev, int32_t* status_dev, double* aux_dev, void* stream);
+
 /* ---- cosmic rays on the e-image (imsim/cosmic_rays.py:paint_cr) ----
  * A footprint of the catalog is a run of spans; a hit paints one footprint (or a run of its spans) at (x0, y0).  Every span
  * pixel lands on image[y0 + row][x0 + col + k] += values[value_offset + k] (k = 0 .. n-1); pixels off the image are dropped.
