@@ -154,6 +154,8 @@ class Optics(C.Structure):
 IMS_FIG_MAX_DEG = 10
 IMS_FIG_NCOEF = (IMS_FIG_MAX_DEG + 1) * (IMS_FIG_MAX_DEG + 2) // 2
 IMS_LAYOUT_PERTURBED = 0xFFFFFFFFFFFFFFFF
+IMS_RESHOOT_RUN = 4096          # photon numbers a workgroup of ims_fft_reshoot's shooting launch owns at a time (include/imsim_hip.h)
+IMS_SLOT_RESHOOT = 25           # the Philox slot of a re-shot photon (csrc/ims_math.h: SLOT_RESHOOT)
 
 
 def fig_row(p):
@@ -351,7 +353,7 @@ EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_
            "ims_count_inexact", "ims_struct_size", "ims_test_math", "ims_opd", "ims_opd_perturbed",
            "ims_paint_cosmic_rays", "ims_test_optical_screen", "ims_trace_field_points", "ims_trace_field_points_perturbed",
            "ims_object_spectra", "ims_psf_moments", "ims_knot_positions", "ims_fft_knots_factor",
-           "ims_fft_image_factor", "ims_psf_profile", "ims_psf_adaptive"]
+           "ims_fft_image_factor", "ims_psf_profile", "ims_psf_adaptive", "ims_fft_reshoot", "ims_fft_reshoot_work_bytes"]
 
 _LIB_PATH = tuning.env("IMSIM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libimsim_hip.so")
 _lib = None
@@ -468,6 +470,10 @@ def load():
     lib.ims_psf_moments.argtypes = [C.POINTER(RenderParams), c_i32, c_vp, c_vp, c_vp, c_vp]
     lib.ims_psf_profile.argtypes = [C.POINTER(RenderParams), c_i32, C.POINTER(PsfProfile), c_vp, c_vp, c_vp, c_vp]
     lib.ims_psf_adaptive.argtypes = [C.POINTER(RenderParams), c_i32, c_i32, c_d, c_vp, c_vp, c_vp, c_vp, c_vp]
+    lib.ims_fft_reshoot_work_bytes.argtypes = [c_i64]
+    lib.ims_fft_reshoot_work_bytes.restype = c_i64
+    lib.ims_fft_reshoot.argtypes = [C.POINTER(FftParams), C.POINTER(RenderParams), c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_d, c_vp,
+                                    c_vp, C.POINTER(Photons), c_vp, c_vp, c_i32, c_i32, c_vp]
     lib.ims_object_spectra.argtypes = [c_vp, c_vp, c_vp, c_vp, c_i32, c_d, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,
                                        c_i32, c_vp, c_vp, c_i64, c_vp]
     _lib = lib

@@ -375,5 +375,8 @@ constexpr uint32_t SLOT_PSF = 2;          // + (component >> 1); component c own
 constexpr uint32_t SLOT_OP = 8;           // + (op index >> 1); op k owns words 2(k&1), 2(k&1)+1
 constexpr uint32_t SLOT_PSF_TIME = 20;    // + component: w0 arrival time drawn by a phase-screen PSF
 constexpr uint32_t SLOT_SENSOR = 24;      // w0,w1 diffusion pair, w2 conversion depth, w3 pixel-not-found coin
+constexpr uint32_t SLOT_RESHOOT = 25;     // photon index = ordinal within a re-shot FFT stamp: w0 wavelength, w1,w2 place inside the pixel
+// (SLOT_OP + (op >> 1) ends at 13 with IMS_MAX_OPS 12, SLOT_PSF_TIME + component at 23 with IMS_MAX_PSF 4: neither reaches 24 or 25)
+static_assert(SLOT_OP + ((12 - 1) >> 1) < SLOT_PSF_TIME && SLOT_PSF_TIME + (4 - 1) < SLOT_SENSOR && SLOT_SENSOR < SLOT_RESHOOT, "RNG slots overlap");
 
 }  // namespace ims

@@ -326,9 +326,36 @@ def kpsf_alias_order(kpsf, extra_ktables=(), n_base=2, pixel_scale=0.2):
 
 class DrawState(tuple):
     """what FftDrawer._upload hands to _run: (rows, obj_t, nfft, kpre, rpre, kpre_t, rpre_t, kbuf, rbuf), in `knots` the device
-    side of a batch's RandomKnots objects and in `images` that of its FITS-stamp objects (None: the batch has none)"""
+    side of a batch's RandomKnots objects and in `images` that of its FITS-stamp objects (None: the batch has none), in `reshoot`
+    the buffers of the re-shooting stage (None: the drawer has no Reshoot)"""
     knots = None
     images = None
+    reshoot = None
+
+
+class Reshoot:
+    """What FftDrawer needs to run stamp.fft_photon_ops over its stamps (ims_fft_reshoot, behind stamp.fft_reshoot): the render
+    parameters of `renderer` -- seed, SED tables, optics, ratio tables, as for the photon path -- with the operator list `ops`
+    ((kind, table, [p0 ..]) tuples, Scene.ops' format; None: the renderer's own chain) in place of the renderer's, and max_flux,
+    GalSim's default 1.  The rows the operators read are the ims_object_t rows of the FFT objects, handed to draw / prepared as
+    `photon_objects` in the order of the FFT rows."""
+
+    def __init__(self, renderer, ops=None, max_flux=1.0):
+        from ._abi import Op
+        P = renderer.bound.params(None, 0, None, 0, renderer.image.data_ptr())
+        if ops is not None:
+            if len(ops) > _abi.IMS_MAX_OPS:
+                raise ValueError("too many photon ops")
+            if any(k in (_abi.IMS_OP_RUBIN_OPTICS, _abi.IMS_OP_RUBIN_DIFFRACTION, _abi.IMS_OP_RUBIN_DIFFRACTION_OPTICS) for k, _, _ in ops) \
+                    and renderer.scene.optics is None:
+                raise ValueError("fft_photon_ops: a Rubin optics operator needs the scene's optics descriptor")
+            P.n_ops = len(ops)
+            for k, (kind, table, p) in enumerate(ops):
+                P.ops[k] = Op(kind, table, (C.c_double * 8)(*(list(p) + [0.0] * (8 - len(p)))))
+                renderer.lib.ims_fill_derived_op(C.byref(P.ops[k]))
+        self.P = P
+        self.max_flux = float(max_flux)
+        self.launches = 0                       # draws that ran the stage
 
 
 def set_spikes(P, diffraction_fft, wavelength, renderer=None):
@@ -494,12 +521,16 @@ class FftDrawer:
     """Batched FFT rendering into a Renderer's CCD image."""
 
     def __init__(self, renderer, kpsf, sersic_indices=(1.0, 4.0), add_noise=True, diffraction_fft=None, wavelength=622.2,
-                 extra_ktables=()):
+                 extra_ktables=(), reshoot=None):
         """extra_ktables: radial k-tables on the common q grid appended after the profile tables (the
         VonKarman / Airy tables of atmospheric_fft_kpsf, addressed by IMS_KPSF_TABLE components).  The k-tables of the
         scene's further Sersic indices (Scene.sersic_extra_n, configs.add_sersic_tables) follow behind those:
-        profile_ktable_ids maps an object's radial table id to its k-table id."""
+        profile_ktable_ids maps an object's radial table id to its k-table id.
+        reshoot: a Reshoot (stamp.fft_photon_ops behind stamp.fft_reshoot) or None: with it every draw turns the stamps into photons
+        after the inverse transforms, runs the operators over them and bins them back (ims_fft_reshoot) before the spike and finish
+        steps, and draw / prepared need the batch's photon_objects."""
         self.r = renderer
+        self.reshoot = reshoot
         self.torch = renderer.torch
         extra_n = tuple(getattr(renderer.scene, "sersic_extra_n", ()) or ())
         tabs = [tables.sersic_ktable(n) for n in sersic_indices]
@@ -512,18 +543,20 @@ class FftDrawer:
         self.image_launches = 0                 # draws that ran the stamp pass (ims_fft_image_factor; no stamp row, no launch)
         set_spikes(self.P, diffraction_fft, wavelength, renderer)
 
-    def draw(self, fft_objects, realized=None, knots=None, images=None):
+    def draw(self, fft_objects, realized=None, knots=None, images=None, photon_objects=None):
         """fft_objects: FFT_OBJECT_DTYPE rows sorted by nfft (build_fft_objects).  `realized`:
         optional float64 device tensor [n].  knots: knot_side_arrays of the rows (stamp.fft_knots), None without RandomKnots objects.
-        images: image_side_arrays of the rows (stamp.fft_stamps), None without FITS-stamp objects."""
+        images: image_side_arrays of the rows (stamp.fft_stamps), None without FITS-stamp objects.
+        photon_objects: the OBJECT_DTYPE rows of the same catalog objects in the order of the FFT rows (objects[order] of
+        build_fft_objects); needed by a drawer with a Reshoot, ignored otherwise."""
         if len(fft_objects) == 0:
             return
-        return self._run(self._upload(fft_objects, knots, images), realized)
+        return self._run(self._upload(fft_objects, knots, images, photon_objects), realized)
 
-    def prepared(self, fft_objects, knots=None, images=None):
+    def prepared(self, fft_objects, knots=None, images=None, photon_objects=None):
         """Upload the rows and allocate the k-space / real-space buffers once; returns a zero-argument callable that
         draws the batch (bench.py: the timed region starts with its inputs resident in HBM)."""
-        state = self._upload(fft_objects, knots, images)
+        state = self._upload(fft_objects, knots, images, photon_objects)
 
         def launch():
             self._run(state, None)
@@ -533,12 +566,13 @@ class FftDrawer:
         launch.kspace_elements = int(np.sum(nfft * (nfft // 2 + 1)))
         return launch
 
-    def prepared_chunked(self, fft_objects, max_pixels=1 << 30, images=None):
+    def prepared_chunked(self, fft_objects, max_pixels=1 << 30, images=None, photon_objects=None):
         """`prepared` for a table whose buffers do not fit at once (thousands of bright stars on 1024^2 .. 4096^2 grids: 24 B per grid
         point): the rows -- grouped by FFT size, as build_fft_objects leaves them -- are cut into consecutive chunks of at most
         max_pixels grid points that share ONE set of k-space / real-space / spike buffers and are drawn one after the other on the
         current stream.  Same launches per chunk as `prepared`; returns a zero-argument callable.  images: image_side_arrays of the
-        rows; every chunk carries the part of its own rows."""
+        rows; every chunk carries the part of its own rows.  photon_objects: as for draw; the chunks share ONE second real-space
+        buffer and one work buffer of the re-shooting stage too."""
         torch, r = self.torch, self.r
         rows = np.ascontiguousarray(fft_objects, dtype=FFT_OBJECT_DTYPE)
         nfft = rows["nfft"].astype(np.int64)
@@ -560,6 +594,7 @@ class FftDrawer:
             if self.P.spikes.enabled else None
         self._spike_list = self._make_spike_list(r_need) if self.P.spikes.enabled else None
         from .engine import upload_async
+        shared = self._reshoot_buffers(r_need) if self.reshoot is not None else None
         states = []
         for a, b in spans:
             part = rows[a:b].copy()
@@ -572,6 +607,8 @@ class FftDrawer:
                                kbuf[:int(kpre[-1])], rbuf[:int(rpre[-1])]))
             if images is not None and np.any(np.asarray(images[a:b]) >= 0):
                 state.images = self._upload_images(part, np.asarray(images)[a:b])
+            if self.reshoot is not None:
+                state.reshoot = self._upload_reshoot(part, None if photon_objects is None else photon_objects[a:b], shared)
             states.append(state)
 
         def launch():
@@ -583,10 +620,32 @@ class FftDrawer:
         launch.chunks = len(states)
         launch.pixels = int(px.sum())
         launch.kspace_elements = int(np.sum(nfft * (nfft // 2 + 1)))
-        launch.keep = (states, kbuf, rbuf, spike)
+        launch.keep = (states, kbuf, rbuf, spike, shared)
         return launch
 
-    def _upload(self, fft_objects, knots=None, images=None):
+    def _reshoot_buffers(self, n_pix):
+        """the second real-space buffer and the work buffer of ims_fft_reshoot for up to n_pix grid points"""
+        torch, r = self.torch, self.r
+        need = int(r.lib.ims_fft_reshoot_work_bytes(int(n_pix)))
+        if need < 0:
+            raise _abi.ImsimHipError("ims_fft_reshoot_work_bytes: " + r.lib.ims_last_error().decode())
+        return (torch.empty(int(n_pix), dtype=torch.float64, device=r.device), torch.empty(need, dtype=torch.uint8, device=r.device))
+
+    def _upload_reshoot(self, rows, photon_objects, shared=None):
+        """the device side of a batch's re-shooting stage: the ims_object_t rows of the FFT rows, the output and work buffers
+        (shared: those of prepared_chunked), and the host copy of the FFT rows the entry point checks"""
+        torch, r = self.torch, self.r
+        from .engine import upload_async
+        if photon_objects is None or len(photon_objects) != len(rows):
+            raise ValueError("a drawer with a Reshoot needs photon_objects: one OBJECT_DTYPE row per FFT row, in their order")
+        po = np.ascontiguousarray(photon_objects, dtype=_abi.OBJECT_DTYPE)
+        if not np.array_equal(po["obj_id"], rows["obj_id"]):
+            raise ValueError("photon_objects: not the rows of the FFT rows' objects (obj_id differs)")
+        n_pix = int(np.sum(rows["nfft"].astype(np.int64) ** 2))
+        out, work = shared if shared is not None else self._reshoot_buffers(n_pix)
+        return dict(rows=rows, po=upload_async(torch, r.device, po.view(np.uint8).reshape(-1)), out=out[:n_pix], work=work)
+
+    def _upload(self, fft_objects, knots=None, images=None, photon_objects=None):
         torch, r = self.torch, self.r
         rows = np.ascontiguousarray(fft_objects, dtype=FFT_OBJECT_DTYPE)
         from .engine import upload_async
@@ -607,6 +666,8 @@ class FftDrawer:
             state.knots = self._upload_knots(rows, knots)
         if images is not None and np.any(np.asarray(images) >= 0):
             state.images = self._upload_images(rows, images)
+        if self.reshoot is not None:
+            state.reshoot = self._upload_reshoot(rows, photon_objects)
         return state
 
     def _upload_images(self, rows, images):
@@ -726,6 +787,17 @@ class FftDrawer:
                 # the library's own hipFFT plans (ims_fft_inverse): nothing of the branch needs a Python-side transform
                 _abi.check(inverse(kbuf.data_ptr() + 16 * int(kpre[a]), rbuf.data_ptr() + 8 * int(rpre[a]), int(size), b - a, st),
                            "ims_fft_inverse")
+        rs = getattr(state, "reshoot", None)
+        if rs is not None:
+            # stamp.fft_photon_ops (behind stamp.fft_reshoot): the stamps as photons through the operators and back into a second
+            # buffer, which holds the image itself (no 1 / N^2 left to apply)
+            R = self.reshoot
+            _abi.check(r.lib.ims_fft_reshoot(C.byref(P), C.byref(R.P), obj_t.data_ptr(), rs["rows"].ctypes.data, rs["po"].data_ptr(), n,
+                                             rpre_t.data_ptr(), int(rpre[-1]), rbuf.data_ptr(), int(raw), R.max_flux,
+                                             rs["work"].data_ptr(), rs["out"].data_ptr(), None, None, None, 0, 0, st), "ims_fft_reshoot")
+            R.launches += 1
+            rbuf = rs["out"]
+            raw = False
         final = rbuf
         bbox = None
         if P.spikes.enabled:
@@ -752,5 +824,6 @@ class FftDrawer:
         # _last until they are through): the saturated-region boxes too -- freed at the end of this call, their block went back to
         # the allocator and to the next CCD's uploads while k_fft_bbox / k_fft_spikes were still queued (round 5: the rows of the
         # next CCD's k-space fill overwritten, a fault or a hang once the side stream ran behind)
-        self._last = (kbuf, rbuf, final, obj_t, kpre_t, rpre_t, bbox, getattr(self, "_spike_list", None), kn, im)
+        # (with a Reshoot, rbuf is the stage's output; the transforms' own buffer, its input, and the stage's rows follow at the end)
+        self._last = (kbuf, rbuf, final, obj_t, kpre_t, rpre_t, bbox, getattr(self, "_spike_list", None), kn, im, rs, state[8])
         return kspace, rbuf

@@ -173,6 +173,8 @@ class CcdJob:
     fft_rows: Optional[np.ndarray] = None              # FFT_OBJECT_DTYPE rows sorted by FFT size (fft_draw.build_fft_objects)
     fft_knots: Optional[tuple] = None                  # fft_draw.knot_side_arrays of fft_rows (stamp.fft_knots; None: no RandomKnots row)
     fft_images: Optional[np.ndarray] = None            # fft_draw.image_side_arrays of fft_rows (stamp.fft_stamps; None: no FITS-stamp row)
+    fft_photon_ops: Optional[list] = None              # stamp.fft_photon_ops behind stamp.fft_reshoot: (kind, table, [p ..]) tuples, or None
+    fft_photon_objects: Optional[np.ndarray] = None    # with them: the OBJECT_DTYPE rows of fft_rows' objects, in the order of fft_rows
     kpsf: Optional[list] = None                        # k-space PSF of the FFT drawer
     extra_ktables: tuple = ()
     diffraction_fft: "object" = None
@@ -215,10 +217,11 @@ def draw_job(renderer, job, realized=None, fft_stream=None, defer=False):
         side = fft_stream if (fft_stream is not None and fft_stream != main) else None
         # tables, buffers and uploads under the caller's stream (whose cached blocks fit: a buffer allocated under another stream
         # comes out of hipMalloc, a device-wide synchronisation); only the launches go to the side stream
+        reshoot = fft_draw.Reshoot(renderer, job.fft_photon_ops) if job.fft_photon_ops else None
         drawer = fft_draw.FftDrawer(renderer, job.kpsf, add_noise=True, diffraction_fft=job.diffraction_fft,
-                                    wavelength=job.wavelength, extra_ktables=job.extra_ktables)
+                                    wavelength=job.wavelength, extra_ktables=job.extra_ktables, reshoot=reshoot)
         r_fft = torch.zeros(job.n_fft, dtype=torch.float64, device=renderer.device) if realized is not None else None
-        state = drawer._upload(job.fft_rows, job.fft_knots, job.fft_images)
+        state = drawer._upload(job.fft_rows, job.fft_knots, job.fft_images, job.fft_photon_objects)
         if side is not None:
             side.wait_stream(main)                                # the renderer's scene tables, its zeroed image, the uploads above
         with torch.cuda.stream(side if side is not None else main):
@@ -270,13 +273,15 @@ class LSST_ImageBuilder(LSST_ImageBuilderBase):
 
     def prepare(self, scene, cat, phot_flux, make_objects, fft_sb_thresh=0.0, max_flux_simple=100.0,
                 draw_method="auto", kpsf=None, fwhm_total=0.8, diffraction_fft=None, wavelength=622.2,
-                nrecalc=None, extra_ktables=(), vignetting=None, sky=None, fft_knots=False, fft_stamps=False):
+                nrecalc=None, extra_ktables=(), vignetting=None, sky=None, fft_knots=False, fft_stamps=False, fft_photon_ops=None):
         """Host half of the draw loop: which objects exist (SkipThisObject for phot_flux == 0, stamp.py:199-202), FFT /
         photons / faint for each (stamp.py:275-336), the rows of both kinds.  Nothing here touches the GPU.
         fft_knots (stamp.fft_knots, an extension, off by default): RandomKnots objects above the threshold take the FFT branch as the
         reference's do -- unless the PSF has aliases to fold (fft_draw.has_kspace_form).
         fft_stamps (stamp.fft_stamps, an extension, off by default): the same for FITS-stamp objects (scene.image_profiles), which
-        must also fit the grid their stamp size gives them."""
+        must also fit the grid their stamp size gives them.
+        fft_photon_ops (stamp.fft_photon_ops behind stamp.fft_reshoot; None or empty: no such stage): the operators the FFT-drawn
+        stamps are re-shot through (fft_draw.Reshoot); the job then keeps the photon rows of its FFT objects beside the FFT rows."""
         n_all = len(cat["x"])
         if self.nobjects is not None:
             n_all = min(n_all, int(self.nobjects))
@@ -320,6 +325,8 @@ class LSST_ImageBuilder(LSST_ImageBuilderBase):
                 job.fft_knots = fft_draw.knot_side_arrays(fobj, order)
             if fft_stamps and (fobj["prof_table"] == IMS_PROF_IMAGE).any():
                 job.fft_images = fft_draw.image_side_arrays(fobj, order)
+            if fft_photon_ops:
+                job.fft_photon_ops, job.fft_photon_objects = list(fft_photon_ops), fobj[order]
             job.fft_index = np.flatnonzero(fft_rows)[order]
             fft_flux[np.flatnonzero(fft_rows)] = fflux
         job.host = dict(sel=sel, keep=keep, sub=sub, nominal=nominal, phot=phot, fft_rows=fft_rows, faint=faint, fft_flux=fft_flux)
@@ -327,7 +334,7 @@ class LSST_ImageBuilder(LSST_ImageBuilderBase):
 
     def build_image(self, renderer, cat, phot_flux, make_objects, fft_sb_thresh=0.0, max_flux_simple=100.0,
                     draw_method="auto", kpsf=None, fwhm_total=0.8, diffraction_fft=None, wavelength=622.2,
-                    nrecalc=None, truth=None, extra_ktables=(), vignetting=None, fft_knots=False, fft_stamps=False):
+                    nrecalc=None, truth=None, extra_ktables=(), vignetting=None, fft_knots=False, fft_stamps=False, fft_photon_ops=None):
         """The draw loop (imsim/lsst_image.py:342-368 + imsim/stamp.py:411-575).
 
         cat / phot_flux: catalog dict and Poisson-realised fluxes; make_objects(cat, phot) builds the
@@ -336,7 +343,7 @@ class LSST_ImageBuilder(LSST_ImageBuilderBase):
         job = self.prepare(renderer.scene, cat, phot_flux, make_objects, fft_sb_thresh=fft_sb_thresh, max_flux_simple=max_flux_simple,
                            draw_method=draw_method, kpsf=kpsf, fwhm_total=fwhm_total, diffraction_fft=diffraction_fft,
                            wavelength=wavelength, nrecalc=nrecalc, extra_ktables=extra_ktables, vignetting=vignetting,
-                           fft_knots=fft_knots, fft_stamps=fft_stamps)
+                           fft_knots=fft_knots, fft_stamps=fft_stamps, fft_photon_ops=fft_photon_ops)
         realized = renderer.torch.zeros(job.n_kept, dtype=renderer.torch.float64, device=renderer.device)
         draw_job(renderer, job, realized=realized)
         if truth is not None:
@@ -367,7 +374,7 @@ class LSST_PhotonPoolingImageBuilder(LSST_ImageBuilderBase):
 
     def build_image(self, renderer, cat, phot_flux, make_objects, max_flux_simple=100.0, seed=0, truth=None, fft_sb_thresh=0.0,
                     kpsf=None, fwhm_total=0.8, diffraction_fft=None, wavelength=622.2, extra_ktables=(), vignetting=None,
-                    checkpoint=None, fft_knots=False, fft_stamps=False):
+                    checkpoint=None, fft_knots=False, fft_stamps=False, fft_photon_ops=None):
         """LSST_PhotonPoolingImageBuilder.buildImage (imsim/photon_pooling.py:29-174): the fluxes of all objects are known
         up front, so the objects are partitioned into FFT / photon-shooting / faint; the FFT objects are drawn FIRST
         (:84-114, in nbatch_fft batches over objects), then the photon batches run through the pooled path."""
@@ -399,8 +406,10 @@ class LSST_PhotonPoolingImageBuilder(LSST_ImageBuilderBase):
             if kpsf is None:
                 raise GalSimConfigError("FFT drawing needs the k-space PSF description")
             idx_fft = np.flatnonzero(fft_rows)
+            # stamp.fft_photon_ops behind stamp.fft_reshoot: the FFT-first pass re-shoots its stamps through these operators
+            reshoot = fft_draw.Reshoot(renderer, list(fft_photon_ops)) if fft_photon_ops else None
             drawer = fft_draw.FftDrawer(renderer, kpsf, add_noise=True, diffraction_fft=diffraction_fft, wavelength=wavelength,
-                                        extra_ktables=extra_ktables)
+                                        extra_ktables=extra_ktables, reshoot=reshoot)
             nb = max(min(self.nbatch_fft, len(idx_fft)), 1)
             for batch in photon_pooling.make_batches(list(idx_fft), nb):
                 if not batch:
@@ -416,7 +425,7 @@ class LSST_PhotonPoolingImageBuilder(LSST_ImageBuilderBase):
                 r_fft = torch.zeros(len(rows), dtype=torch.float64, device=renderer.device)
                 knots = fft_draw.knot_side_arrays(fobj, order) if fft_knots and (fobj["prof_table"] == IMS_PROF_KNOTS).any() else None
                 images = fft_draw.image_side_arrays(fobj, order) if fft_stamps and (fobj["prof_table"] == IMS_PROF_IMAGE).any() else None
-                drawer.draw(rows, realized=r_fft, knots=knots, images=images)
+                drawer.draw(rows, realized=r_fft, knots=knots, images=images, photon_objects=fobj[order] if reshoot is not None else None)
                 realized.index_add_(0, torch.from_numpy(batch[order]).to(renderer.device), r_fft)
                 fft_flux[batch] = fflux
             if checkpoint is not None:

@@ -69,7 +69,10 @@ class LSST_SiliconBuilder:
     Every draw builds a small renderer: milliseconds per object -- the batch path is the fast one."""
 
     def __init__(self, scene, make_objects, kpsf=None, fwhm_total=0.8, fft_sb_thresh=0.0, max_flux_simple=100.0,
-                 diffraction_fft=None, wavelength=622.2, extra_ktables=(), nrecalc=None, device="cuda:0"):
+                 diffraction_fft=None, wavelength=622.2, extra_ktables=(), nrecalc=None, device="cuda:0", fft_photon_ops=None):
+        """fft_photon_ops (stamp.fft_photon_ops behind stamp.fft_reshoot; None: no such stage): the operators an FFT-drawn stamp is
+        re-shot through, as lsst_image.draw_job does for a CCD's FFT objects"""
+        self.fft_photon_ops = list(fft_photon_ops) if fft_photon_ops else None
         self.scene, self.make_objects = scene, make_objects
         self.kpsf, self.fwhm_total, self.fft_sb_thresh, self.max_flux_simple = kpsf, fwhm_total, fft_sb_thresh, max_flux_simple
         self.diffraction_fft, self.wavelength, self.extra_ktables = diffraction_fft, wavelength, tuple(extra_ktables)
@@ -146,9 +149,11 @@ class LSST_SiliconBuilder:
             if self.kpsf is None:
                 raise ValueError("FFT drawing needs the k-space PSF description")
             flux = np.array([base["fft_flux"] or base["nominal_flux"]])
-            frows, _ = fft_draw.build_fft_objects(rows, flux, fft_draw.profile_ktable_ids(sc, rows["prof_table"], len(self.extra_ktables)))
+            frows, order = fft_draw.build_fft_objects(rows, flux, fft_draw.profile_ktable_ids(sc, rows["prof_table"], len(self.extra_ktables)))
+            reshoot = fft_draw.Reshoot(r, self.fft_photon_ops) if self.fft_photon_ops else None
             fft_draw.FftDrawer(r, self.kpsf, add_noise=True, diffraction_fft=self.diffraction_fft, wavelength=self.wavelength,
-                               extra_ktables=self.extra_ktables).draw(frows, realized=real)
+                               extra_ktables=self.extra_ktables, reshoot=reshoot).draw(
+                                   frows, realized=real, photon_objects=rows[order] if reshoot is not None else None)
         else:
             r.render_lsst_image(rows, nrecalc=self.nrecalc, realized=real)
         r.synchronize()

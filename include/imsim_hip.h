@@ -736,6 +736,44 @@ int  ims_fft_spikes_listed(const ims_fft_params_t* params, const ims_fft_object_
 int  ims_fft_finish(const ims_fft_params_t* params, const ims_fft_object_t* objects_dev, int64_t n_objects,
                     const int64_t* pix_prefix_dev, int64_t n_pix, const double* rbuf, void* stream);
 
+/* ---- re-shooting FFT-drawn stamps through the photon operators (stamp.fft_photon_ops; imsim/stamp.py:493-499, :675-681) ----
+ * GalSim's drawImage(method='fft', photon_ops=...) turns the noise-free FFT stamp into photons (PhotonArray.makeFromImage), runs the
+ * operators over them and accumulates them into a stamp of the same bounds, without a sensor; the clip, the spikes and the noise
+ * follow.  ims_fft_reshoot is that stage, between the inverse transforms and ims_fft_spikes / ims_fft_finish: it reads rbuf_in
+ * (raw = 1: ims_fft_inverse_raw's buffer, the 1 / nfft^2 applied on reading) and writes out_dev, a second buffer of the same layout
+ * that the later steps read with rbuf_raw = 0; everything outside an object's stamp rectangle is zero there.
+ *   photons   the stamp's pixels row-major (y ascending, x ascending inside); a pixel of value v spawns N = 0 photons if v == 0,
+ *             1 if |v| <= max_flux, else ceil(|v| / max_flux), of flux v / N each (negative for a negative pixel); a value that is not
+ *             finite spawns none.  (Stated from GalSim's source; max_flux = 1 is GalSim's default.)
+ *   identity  photon k of an object, k = the exclusive prefix of N over the stamp plus the index inside the pixel, draws the Philox
+ *             block (seed, obj_id, k, slot 25): w0 the wavelength as ims_shoot_* draw it (sed_table / sed_wave of the object's
+ *             ims_object_t row), x = px + (w01(w1) - 1/2), y = py + (w01(w2) - 1/2) in CCD pixels (centres at integers); dxdz, dydz,
+ *             pupil_u, pupil_v, time start at 0.  Then the operator chain of render_params on row photon_objects_dev[i] -- the
+ *             ims_object_t row of the catalog object of FFT row i -- with photon number k.  render_params' PSF list, object table and
+ *             segments are not used.
+ *   binning   flux == 0: lost.  Pixel (floor(x + 1/2), floor(y + 1/2)); outside the stamp rectangle: lost.  The deposit is the integer
+ *             llrint(flux * 2^32), summed with 64-bit integer atomics in out_dev itself and turned into doubles (x 2^-32) by a last
+ *             pass: the result does not depend on the order of arrival, the grid size or the run length.  |sum| < 2^31 e- per pixel
+ *             keeps the sums inside an int64: a row whose |flux| is 2^31 or more is refused.
+ * fft_objects_host: the same rows on the host (flux, geometry and offsets are checked before anything is launched).  work_dev: device
+ * scratch of ims_fft_reshoot_work_bytes(n_pix) bytes (the per-tile photon counts and their scan; n_pix a multiple of 1024: grids are
+ * powers of two from 32).  pool_stage 1 / 2: every photon is also stored as made / after the operators in pool_out (x, y, flux, dxdz,
+ * dydz, wavelength; pupil_u, pupil_v, time and obj_index -- the FFT row -- where not NULL) at pool_offset_dev[i] + k, and land_dev
+ * (int32, may be NULL) gets the grid point gy * nfft + gx it was added to, -1 for a lost photon; a photon whose place is at or beyond
+ * pool_offset_dev[i + 1] or pool_out->n is not stored.  pool_stage 0: pool_out, pool_offset_dev and land_dev are NULL.
+ * grid: workgroups of the shooting launch, 0 = the library's choice (for tests: the result does not depend on it).
+ * The shooting workgroups own runs of IMS_RESHOOT_RUN consecutive photon numbers; the photon total stays on the device.
+ * IMS_ERR_ARG before any HIP call for a NULL argument, max_flux <= 0, pool_stage outside 0 .. 2, a pool with n < 1, rows that fail the
+ * checks above; n_objects == 0 launches nothing.  Added in ABI version 22 without changing any existing struct or function, so the
+ * version number stays. */
+#define IMS_RESHOOT_RUN 4096
+int64_t ims_fft_reshoot_work_bytes(int64_t n_pix);
+int  ims_fft_reshoot(const ims_fft_params_t* fft_params, const ims_render_params_t* render_params, const ims_fft_object_t* fft_objects_dev,
+                     const ims_fft_object_t* fft_objects_host, const ims_object_t* photon_objects_dev, int64_t n_objects,
+                     const int64_t* r_prefix_dev, int64_t n_pix, const double* rbuf_in, int32_t raw, double max_flux, void* work_dev,
+                     double* out_dev, const ims_photons_t* pool_out, const int64_t* pool_offset_dev, int32_t* land_dev,
+                     int32_t pool_stage, int32_t grid, void* stream);
+
 /* ---- phase-screen gather with managed locality (imsim/atmPSF.py:298-336; N1 of the survey's scope) ----
  * A photon of an AtmosphericPSF reads a 2 x 2 cell of each of the six 8192^2 screens at (pupil position + altitude x field
  * angle - wind x arrival time): a random place on a strip of 84 x (wind x exposure) samples per layer.  Gathered where the
