@@ -340,6 +340,16 @@ class PsfProfile(C.Structure):
     _fields_ = [("n_r", c_i32), ("n_phi", c_i32), ("r2_edge_dev", c_vp), ("dir_dev", c_vp)]
 
 
+class PsfImage(C.Structure):
+    """ims_psf_image_t: the stamp of ims_psf_image (cells and the reciprocal of a cell's side)"""
+    _fields_ = [("nx", c_i32), ("ny", c_i32), ("inv_scale", c_d)]
+
+
+# library-only, like the structs above (the oracle bins no stamps): the last index of ims_struct_size
+PSF_IMAGE_STRUCT_INDEX = 30
+PSF_IMAGE_MAX = 512                  # IMS_PSF_IMAGE_MAX
+
+
 # every symbol include/imsim_hip.h declares
 EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_info", "ims_known_optics_layout", "ims_photon_kernel_variant",
            "ims_tuning_defaults", "ims_get_tuning", "ims_set_tuning", "ims_shoot_accumulate",
@@ -353,7 +363,7 @@ EXPORTS = ["ims_abi_version", "ims_last_error", "ims_device_count", "ims_device_
            "ims_count_inexact", "ims_struct_size", "ims_test_math", "ims_opd", "ims_opd_perturbed",
            "ims_paint_cosmic_rays", "ims_test_optical_screen", "ims_trace_field_points", "ims_trace_field_points_perturbed",
            "ims_object_spectra", "ims_psf_moments", "ims_knot_positions", "ims_fft_knots_factor",
-           "ims_fft_image_factor", "ims_psf_profile", "ims_psf_adaptive", "ims_fft_reshoot", "ims_fft_reshoot_work_bytes"]
+           "ims_fft_image_factor", "ims_psf_profile", "ims_psf_adaptive", "ims_fft_reshoot", "ims_fft_reshoot_work_bytes", "ims_psf_image"]
 
 _LIB_PATH = tuning.env("IMSIM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libimsim_hip.so")
 _lib = None
@@ -395,6 +405,8 @@ def load():
     for k, st in ((OPTICAL_SCREEN_STRUCT_INDEX, OpticalScreen), (ATMOSPHERE_OPTICAL_STRUCT_INDEX, AtmosphereOptical)):
         if lib.ims_struct_size(k) != C.sizeof(st):
             raise ImsimHipError(f"ABI mismatch for {st.__name__}: library {lib.ims_struct_size(k)} bytes, binding {C.sizeof(st)}")
+    if lib.ims_struct_size(PSF_IMAGE_STRUCT_INDEX) != C.sizeof(PsfImage):
+        raise ImsimHipError(f"ABI mismatch for PsfImage: library {lib.ims_struct_size(PSF_IMAGE_STRUCT_INDEX)} bytes, binding {C.sizeof(PsfImage)}")
     lib.ims_shoot_accumulate.argtypes = [C.POINTER(RenderParams), c_vp]
     lib.ims_shoot_photons.argtypes = [C.POINTER(RenderParams), c_vp, C.POINTER(Photons), c_vp]
     lib.ims_apply_ops.argtypes = [C.POINTER(RenderParams), c_vp, C.POINTER(Photons), c_vp]
@@ -469,6 +481,7 @@ def load():
     lib.ims_trace_field_points_perturbed.argtypes = [c_vp, c_vp, c_vp, c_i64, c_d, c_vp, c_i32, c_vp, c_vp, c_vp]
     lib.ims_psf_moments.argtypes = [C.POINTER(RenderParams), c_i32, c_vp, c_vp, c_vp, c_vp]
     lib.ims_psf_profile.argtypes = [C.POINTER(RenderParams), c_i32, C.POINTER(PsfProfile), c_vp, c_vp, c_vp, c_vp]
+    lib.ims_psf_image.argtypes = [C.POINTER(RenderParams), c_i32, C.POINTER(PsfImage), c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.ims_psf_adaptive.argtypes = [C.POINTER(RenderParams), c_i32, c_i32, c_d, c_vp, c_vp, c_vp, c_vp, c_vp]
     lib.ims_fft_reshoot_work_bytes.argtypes = [c_i64]
     lib.ims_fft_reshoot_work_bytes.restype = c_i64

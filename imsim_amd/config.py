@@ -20,7 +20,7 @@ import numpy as np
 import yaml
 
 from . import _abi, atm_psf, catalog, configs, diffraction, fft_draw, instcat, lsst_image, optical_system, optics as opticsmod
-from . import cosmic_rays, flat, opd as opdmod, parallel, psf_map as psfmapmod, psf_profile as psfprofmod, readout, sensor as sensormod, tables, treerings, truth as truthmod, tuning
+from . import cosmic_rays, flat, opd as opdmod, parallel, psf_map as psfmapmod, psf_image as psfimgmod, psf_profile as psfprofmod, readout, sensor as sensormod, tables, treerings, truth as truthmod, tuning
 from .engine import Scene, SensorSetup, make_slots
 from .lsst_image import GalSimConfigError
 
@@ -880,7 +880,7 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     if itype not in valid_image_types:
         raise GalSimConfigError(f"Invalid image type {itype}")
     if itype == "LSST_Flat":
-        for k in ("opd", "sag", "psf_map", "psf_profile"):        # a flat has no telescope to trace, and no PSF
+        for k in ("opd", "sag", "psf_map", "psf_profile", "psf_image"):        # a flat has no telescope to trace, and no PSF
             if k in out:
                 res.ignored.append(f"output.{k}")
         return _process_flat(cfg, ev, image, res, device, data_dir)
@@ -905,6 +905,17 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
             if isinstance(op, dict) and op.get("type") == "BandpassRatio":
                 raise GalSimConfigError("output.psf_profile counts photons unweighted: stage ops cannot run a chain with a BandpassRatio "
                                         "operator (stamp.photon_ops), whose photons carry unequal flux")
+    psf_image_kw = psfimgmod.parse_config(out["psf_image"], ev) if "psf_image" in out else None
+    psf_images = {}                                                     # file name -> [(cube, header, summary, header)], one per CCD
+    if psf_image_kw is not None and psf_image_kw["stage"] != "psf":
+        for op in stamp_cfg.get("photon_ops", []) or []:
+            if isinstance(op, dict) and op.get("type") == "BandpassRatio":
+                raise GalSimConfigError("output.psf_image counts photons unweighted: stages ops and sensor cannot run a chain with a "
+                                        "BandpassRatio operator (stamp.photon_ops), whose photons carry unequal flux")
+    if psf_image_kw is not None and psf_image_kw["stage"] == "sensor":
+        sens = image.get("sensor", "")
+        if not (isinstance(sens, dict) and sens.get("type", "Silicon") == "Silicon"):
+            raise GalSimConfigError("output.psf_image.stage sensor needs a Silicon sensor (image.sensor)")
     catalogs = parse_catalogs(out, ev, itype)
     crs = parse_cosmic_rays(out, ev, data_dir)
     parse_atm_psf_options(inp.get("atm_psf"), stamp_cfg, ev, data_dir, res, itype, cfg.get("psf"))
@@ -1166,6 +1177,13 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
             wl, thr = tables.synthetic_r_band()
             psf_profiles.setdefault(fn, []).append(psfprofmod.ccd_profile(ctx.scene, ctx.det_name, wl_eff=tables.effective_wavelength(wl, thr),
                                                                           device=device, **psf_profile_kw))
+        if psf_image_kw is not None:
+            # output.psf_image: the same photons on the same grid binned into stamps, up to the sensor's conversion and diffusion
+            pi = out["psf_image"]
+            fn = os.path.join(str(ev.value(pi.get("dir", out.get("dir", "")))), str(ev.value(pi["file_name"])))
+            wl, thr = tables.synthetic_r_band()
+            psf_images.setdefault(fn, []).append(psfimgmod.ccd_images(ctx.scene, ctx.det_name, wl_eff=tables.effective_wavelength(wl, thr),
+                                                                      device=device, **psf_image_kw))
         done[ctx.det] = (img, ctx.truth, ctx.det_name, sub)
 
     # Several CCDs of LSST_Image type go through the overlapped focal-plane path (focal_plane.render_focal_plane, the per-CCD
@@ -1212,6 +1230,9 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
         res.files.append(fn)
     for fn, hdus in psf_profiles.items():                # two image HDUs (counts, summary) per CCD that names the file
         psfprofmod.write(fn, hdus)
+        res.files.append(fn)
+    for fn, hdus in psf_images.items():                  # an image HDU (the stamps) and a SUMMARY table per CCD that names the file
+        psfimgmod.write(fn, hdus)
         res.files.append(fn)
     if "sag" in out and rank == 0:
         # the telescope input of the reference holds the camera turned by the rotator (imsim/telescope_loader.py:242-246)

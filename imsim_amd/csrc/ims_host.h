@@ -282,6 +282,7 @@ int ims_struct_size(int which)
     case 27: return (int)sizeof(ims_cr_hit_t);
     case 28: return (int)sizeof(ims_optical_screen_t);
     case 29: return (int)sizeof(ims_atmosphere_optical_t);
+    case 30: return (int)sizeof(ims_psf_image_t);
     }
     return -1;
 }

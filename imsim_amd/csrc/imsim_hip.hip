@@ -4519,6 +4519,7 @@ int ims_trace_field_points_perturbed(const ims_optics_perturbed_t* optics_dev, c
 #include "ims_knots.h"          // RandomKnots on the FFT branch: knot positions and the structure-factor pass
 #include "ims_stamp_fft.h"      // FITS stamps on the FFT branch: the pixel spectrum times the interpolant's transform
 #include "ims_profile.h"        // radial / azimuthal histograms of the delivered PSF (the photons of ims_psf_moments, binned)
+#include "ims_psf_image.h"      // postage stamps of the same photons, binned up to the sensor's conversion and diffusion
 #include "ims_adaptive.h"       // adaptive (elliptical-Gaussian-weighted) moments of the same photons, iterated on the device
 #include "ims_reshoot.h"        // FFT-drawn stamps re-shot through the photon operators (stamp.fft_photon_ops behind stamp.fft_reshoot)
 #include "ims_exchange.h"       // RCCL exchanges between the GPUs of a node

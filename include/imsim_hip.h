@@ -1215,6 +1215,40 @@ typedef struct ims_psf_profile {
 int  ims_psf_profile(const ims_render_params_t* params, int32_t stage, const ims_psf_profile_t* spec, const double* centre_dev,
                      int64_t* counts_dev, int64_t* dropped_dev, void* stream);
 
+/* ---- postage stamps of the delivered PSF at a table of field points, up to the sensor ----
+ * The rows and the photons are those of ims_psf_moments: photon k of a row is the same photon, bit for bit.  Nothing of it is
+ * stored: it adds 1 to one cell of the row's stamp counts_dev[i][iy][ix] (int64 [n][ny][nx]; its flux is not applied, and a chain
+ * with an IMS_OP_BANDPASS_RATIO operator is refused in stages 2 and 3 with IMS_ERR_UNSUPPORTED), to outside_dev[i] when it falls
+ * beside the stamp, or to dropped_dev[i] when it is lost.  The three outputs are zeroed by the call, and per row
+ * sum(counts) + outside + dropped = n_phot.
+ *   stage 1: (dx, dy) is ims_psf_moments' stage-1 offset (arcsec for rows whose winv is the identity).
+ *   stage 2: (dx, dy) = (x - x0, y - y0) after params->ops[] [pixels].
+ *   stage 3: as stage 2; then, for the rows a render would convert (a Silicon params->sensor, the row not IMS_OBJ_FAINT), the
+ *            first half of SiliconSensor.accumulate -- conversion at a depth drawn from the absorption length at the photon's
+ *            wavelength, the lateral walk of an inclined ray down to that depth, charge diffusion -- on the counters and with
+ *            the arguments of ims_shoot_ops_photons into a converted pool: (dx, dy) = the converted position minus (x0, y0)
+ *            [pixels], bit for bit that pool's (x - x0, y - y0).  A photon that converts beyond the back of the sensor is
+ *            dropped, as a photon of flux 0 is in every stage.  Other rows keep their stage-2 offset, as in that pool.
+ *            Stage 3 draws the sensor's own random block only: stages 1 and 2 of the same row are the same photons.
+ *            What stage 3 is not: there is no pixel search.  The stamp bins continuous positions at the conversion depth on a
+ *            regular grid; tree rings and the brighter-fatter effect move pixel BOUNDARIES, not photons, and do not appear.
+ * With centre_dev (f64 [n][2], or NULL) the row's centre is subtracted first, one f64 subtraction per axis, as in ims_psf_profile.
+ * The binning uses f64 products, sums and comparisons only, each rounded once (no contraction, no division on the device):
+ *   u = fl(fl(dx inv_scale) + nx / 2),  v = fl(fl(dy inv_scale) + ny / 2)        (nx / 2, ny / 2 exact in f64)
+ *   0 <= u < nx and 0 <= v < ny: the cell (ix, iy) = (floor(u), floor(v)), so that a photon on a cell's lower edge belongs to
+ *   that cell and the row's centre is the middle of the stamp (a cell's centre for odd sizes, a corner for even ones);
+ *   otherwise (beside the stamp, or u or v not a number): outside_dev[i].
+ * The counts are integer sums: a row's stamp is the same in every call, whatever the launch geometry, the other rows of the
+ * call and their order.  Added in ABI version 22 without changing any existing struct or function, so the version number
+ * stays; ims_psf_image_t is ims_struct_size(30). */
+#define IMS_PSF_IMAGE_MAX 512
+typedef struct ims_psf_image {
+    int32_t nx, ny;                  /* cells of the stamp, 1 .. IMS_PSF_IMAGE_MAX each */
+    double inv_scale;                /* 1 / the side of a cell in the stage's units; finite and positive */
+} ims_psf_image_t;
+int  ims_psf_image(const ims_render_params_t* params, int32_t stage, const ims_psf_image_t* spec, const double* centre_dev,
+                   int64_t* counts_dev, int64_t* outside_dev, int64_t* dropped_dev, void* stream);
+
 /* ---- adaptive moments of the delivered PSF at a table of field points, iterated on the device ----
  * The rows, the stages and the photons are those of ims_psf_moments: photon k of a row is the same photon, bit for bit, and
  * (dx, dy) the same offset.  Per row the call iterates an elliptical Gaussian weight towards the profile (Bernstein & Jarvis 2002;
