@@ -22,7 +22,11 @@ Conventions (batoid is not available here to check its grid against; these are t
   (`mean`).  NaN where a ray was vignetted or lost.
 * Zernikes.  Annular Zernikes in Noll order with Mahajan's normalisation (unit mean square over the annulus
   eps R_outer <= r <= R_outer, R_outer = pupil_size / 2), j = 1 .. jmax <= 66, fitted by least squares to the finite
-  pixels; AZ_jjj in nm.
+  pixels; AZ_jjj in nm.  The fit is the minimum-norm least-squares solution over the finite pixels (what the reference's
+  np.linalg.lstsq on the basis returns): every coefficient is 0 for a map without a finite pixel (a field outside the field
+  of view, a lost chief ray), and where fewer pixels are finite than terms are fitted it is the pseudo-inverse's solution.
+  It is taken from the device's normal equations (solve_normal): eigenvalues of A^T A below jmax 8192 2^-52 of the largest,
+  the bound of the device sums' rounding, count as zero.
 
 A perturbed telescope (optics.apply_perturbations: shifted, rotated or figured surfaces) is traced surface by surface in
 each surface's frame (ims_opd_perturbed); the path lengths and the reference sphere are taken in telescope coordinates.
@@ -206,6 +210,22 @@ def write(file_name, images):
 
 
 # ---------------- GPU ----------------
+# eigenvalues of A^T A below this fraction of the largest per Zernike term are rounding: an entry of the device's sums is an fma
+# chain over a chunk of 4096 pixels followed by up to 4096 chunk partials, 8192 roundings of 2^-52 at the size of the largest
+# eigenvalue, and the matrix norm of jmax x jmax such entries is at most jmax times that
+NORMAL_RCOND_PER_TERM = 8192 * 2.0 ** -52
+
+
+def solve_normal(ata, atw):
+    """The least-squares coefficients from the normal equations, as the minimum-norm solution (the module docstring's rule):
+    all zeros for a map without a finite pixel, the pseudo-inverse's answer where fewer pixels are finite than terms are
+    fitted, the plain solution otherwise.  Never raises on a singular system."""
+    ata, atw = np.asarray(ata, dtype=np.float64), np.asarray(atw, dtype=np.float64)
+    if not np.any(ata):
+        return np.zeros(len(atw))
+    return np.linalg.lstsq(ata, atw, rcond=len(atw) * NORMAL_RCOND_PER_TERM)[0]
+
+
 def _run(lib, torch, dev, opt_dev, tel, dirs, nx, dx, wavelength, sphere_radius, reference, eps, jmax):
     """one ims_opd call: (maps [n, nx, nx], zk [n, jmax] or None)"""
     n = len(dirs)
@@ -246,7 +266,7 @@ def _run(lib, torch, dev, opt_dev, tel, dirs, nx, dx, wavelength, sphere_radius,
         A = np.zeros((jmax, jmax))
         A[iu] = ata_h[f]
         A = A + np.triu(A, 1).T
-        zk[f] = np.linalg.solve(A, atw_h[f])
+        zk[f] = solve_normal(A, atw_h[f])
     return maps_h, zk
 
 
