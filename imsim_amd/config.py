@@ -824,7 +824,29 @@ def parse_image_wcs(image, res=None):
     return wcs_cfg
 
 
-def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=None, logger=None, rank=0, world=1):
+# The PSF probes among the extra outputs: (config key, module, per-CCD function, writer), in the order their files are listed.
+# A probe's module gives parse_config, and FLUX_STAGES where it counts photons unweighted.
+PSF_PROBES = (("psf_map", psfmapmod, psfmapmod.ccd_map, psfmapmod.write),
+              ("psf_profile", psfprofmod, psfprofmod.ccd_profile, psfprofmod.write),
+              ("psf_image", psfimgmod, psfimgmod.ccd_images, psfimgmod.write))
+
+
+def _refuse_probe_config(key, mod, stage, stamp_cfg, image):
+    """What a probe's launch would refuse and the config alone decides: raised as config errors, before any GPU work"""
+    flux_stages = getattr(mod, "FLUX_STAGES", ())
+    if stage in flux_stages:
+        for op in stamp_cfg.get("photon_ops", []) or []:
+            if isinstance(op, dict) and op.get("type") == "BandpassRatio":
+                words = ("stages " if len(flux_stages) > 1 else "stage ") + " and ".join(flux_stages)
+                raise GalSimConfigError(f"output.{key} counts photons unweighted: {words} cannot run a chain with a BandpassRatio "
+                                        "operator (stamp.photon_ops), whose photons carry unequal flux")
+    if stage == "sensor":
+        sens = image.get("sensor", "")
+        if not (isinstance(sens, dict) and sens.get("type", "Silicon") == "Silicon"):
+            raise GalSimConfigError(f"output.{key}.stage sensor needs a Silicon sensor (image.sensor)")
+
+
+def Process(config,template_dirs=(), overrides=None, device="cuda:0", data_dir=None, logger=None, rank=0, world=1):
     """galsim.config.Process restricted to this path: reads inputs, then for every requested CCD
     builds the scene and runs the image builder on the GPU.  Returns a ProcessResult.
 
@@ -880,7 +902,7 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     if itype not in valid_image_types:
         raise GalSimConfigError(f"Invalid image type {itype}")
     if itype == "LSST_Flat":
-        for k in ("opd", "sag", "psf_map", "psf_profile", "psf_image"):        # a flat has no telescope to trace, and no PSF
+        for k in ("opd", "sag") + tuple(p[0] for p in PSF_PROBES):             # a flat has no telescope to trace, and no PSF
             if k in out:
                 res.ignored.append(f"output.{k}")
         return _process_flat(cfg, ev, image, res, device, data_dir)
@@ -896,26 +918,12 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
     seed = int(ev.value(image.get("random_seed", meta.get("seed", 0))))
     dets = parallel.shard_ccds(range(first, first + nfiles), rank, world)
     opd_kw = parse_opd(out["opd"], ev) if "opd" in out else None     # config errors before any GPU work
-    psf_map_kw = psfmapmod.parse_config(out["psf_map"], ev) if "psf_map" in out else None
-    psf_maps = {}                                                       # file name -> [(cube, header)], one per CCD
-    psf_profile_kw = psfprofmod.parse_config(out["psf_profile"], ev) if "psf_profile" in out else None
-    psf_profiles = {}                                                   # file name -> [(cube, header, summary, header)], one per CCD
-    if psf_profile_kw is not None and psf_profile_kw["stage"] == "ops":
-        for op in stamp_cfg.get("photon_ops", []) or []:
-            if isinstance(op, dict) and op.get("type") == "BandpassRatio":
-                raise GalSimConfigError("output.psf_profile counts photons unweighted: stage ops cannot run a chain with a BandpassRatio "
-                                        "operator (stamp.photon_ops), whose photons carry unequal flux")
-    psf_image_kw = psfimgmod.parse_config(out["psf_image"], ev) if "psf_image" in out else None
-    psf_images = {}                                                     # file name -> [(cube, header, summary, header)], one per CCD
-    if psf_image_kw is not None and psf_image_kw["stage"] != "psf":
-        for op in stamp_cfg.get("photon_ops", []) or []:
-            if isinstance(op, dict) and op.get("type") == "BandpassRatio":
-                raise GalSimConfigError("output.psf_image counts photons unweighted: stages ops and sensor cannot run a chain with a "
-                                        "BandpassRatio operator (stamp.photon_ops), whose photons carry unequal flux")
-    if psf_image_kw is not None and psf_image_kw["stage"] == "sensor":
-        sens = image.get("sensor", "")
-        if not (isinstance(sens, dict) and sens.get("type", "Silicon") == "Silicon"):
-            raise GalSimConfigError("output.psf_image.stage sensor needs a Silicon sensor (image.sensor)")
+    probes = []             # the PSF probes the config names: (key, per-CCD function, writer, keywords, file name -> [one item per CCD])
+    for key, mod, per_ccd, write in PSF_PROBES:
+        if key in out:
+            kw = mod.parse_config(out[key], ev)
+            _refuse_probe_config(key, mod, kw["stage"], stamp_cfg, image)
+            probes.append((key, per_ccd, write, kw, {}))
     catalogs = parse_catalogs(out, ev, itype)
     crs = parse_cosmic_rays(out, ev, data_dir)
     parse_atm_psf_options(inp.get("atm_psf"), stamp_cfg, ev, data_dir, res, itype, cfg.get("psf"))
@@ -1162,28 +1170,14 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
         img = renderer.image_numpy()                         # the e-image as rendered: the readout chain bleeds the device image in place
         _process_outputs(out, ev, sub, renderer.image, ctx.det_name, meta, ctx.seed_ccd)
         _write_catalogs(catalogs, ev, out, ctx.truth, ctx.cat, ctx.scene.optics.img_wcs, sub)
-        if psf_map_kw is not None:
-            # output.psf_map: the moments of the PSF this CCD was rendered with, on a grid over its pixels (evaluated here, where
-            # det_name and the sequence index are the CCD's)
-            pm = out["psf_map"]
-            fn = os.path.join(str(ev.value(pm.get("dir", out.get("dir", "")))), str(ev.value(pm["file_name"])))
+        if probes:
+            # the PSF this CCD was rendered with, on a grid over its pixels: its moments, its radial / azimuthal histograms and its
+            # stamps, of the same photons (the file names are evaluated here, where det_name and the sequence index are the CCD's)
             wl, thr = tables.synthetic_r_band()
-            psf_maps.setdefault(fn, []).append(psfmapmod.ccd_map(ctx.scene, ctx.det_name, wl_eff=tables.effective_wavelength(wl, thr),
-                                                                 device=device, **psf_map_kw))
-        if psf_profile_kw is not None:
-            # output.psf_profile: radial / azimuthal histograms of the same photons on the same grid
-            pp = out["psf_profile"]
-            fn = os.path.join(str(ev.value(pp.get("dir", out.get("dir", "")))), str(ev.value(pp["file_name"])))
-            wl, thr = tables.synthetic_r_band()
-            psf_profiles.setdefault(fn, []).append(psfprofmod.ccd_profile(ctx.scene, ctx.det_name, wl_eff=tables.effective_wavelength(wl, thr),
-                                                                          device=device, **psf_profile_kw))
-        if psf_image_kw is not None:
-            # output.psf_image: the same photons on the same grid binned into stamps, up to the sensor's conversion and diffusion
-            pi = out["psf_image"]
-            fn = os.path.join(str(ev.value(pi.get("dir", out.get("dir", "")))), str(ev.value(pi["file_name"])))
-            wl, thr = tables.synthetic_r_band()
-            psf_images.setdefault(fn, []).append(psfimgmod.ccd_images(ctx.scene, ctx.det_name, wl_eff=tables.effective_wavelength(wl, thr),
-                                                                      device=device, **psf_image_kw))
+            wl_eff = tables.effective_wavelength(wl, thr)
+            for key, per_ccd, _, kw, files in probes:
+                fn = os.path.join(str(ev.value(out[key].get("dir", out.get("dir", "")))), str(ev.value(out[key]["file_name"])))
+                files.setdefault(fn, []).append(per_ccd(ctx.scene, ctx.det_name, wl_eff=wl_eff, device=device, **kw))
         done[ctx.det] = (img, ctx.truth, ctx.det_name, sub)
 
     # Several CCDs of LSST_Image type go through the overlapped focal-plane path (focal_plane.render_focal_plane, the per-CCD
@@ -1225,15 +1219,10 @@ def Process(config, template_dirs=(), overrides=None, device="cuda:0", data_dir=
         res.eimages += sub.eimages
         res.raw += sub.raw
         res.files += sub.files
-    for fn, hdus in psf_maps.items():                    # one image HDU per CCD that names the file
-        psfmapmod.write(fn, hdus)
-        res.files.append(fn)
-    for fn, hdus in psf_profiles.items():                # two image HDUs (counts, summary) per CCD that names the file
-        psfprofmod.write(fn, hdus)
-        res.files.append(fn)
-    for fn, hdus in psf_images.items():                  # an image HDU (the stamps) and a SUMMARY table per CCD that names the file
-        psfimgmod.write(fn, hdus)
-        res.files.append(fn)
+    for _, _, write, _, files in probes:                 # maps, then profiles, then stamps: the CCDs that name a file share it
+        for fn, hdus in files.items():
+            write(fn, hdus)
+            res.files.append(fn)
     if "sag" in out and rank == 0:
         # the telescope input of the reference holds the camera turned by the rotator (imsim/telescope_loader.py:242-246)
         _process_sag(out["sag"], ev, out, opticsmod.with_camera_rotation(build_telescope(tel_cfg, ev, band),

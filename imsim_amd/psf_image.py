@@ -13,18 +13,20 @@ appear in it.
 
 Layout of a point's stamp, counts[iy][ix]: cell ix covers [ix - nx / 2, ix + 1 - nx / 2) * scale around the centre along x,
 lower edge included (the binning rule of include/imsim_hip.h); photons beside the stamp are counted in n_outside, lost photons
-(vignetted, the ray failed, converted beyond the back of the sensor) in n_dropped.  This module holds the host half: the launch
-and two small estimators."""
+(vignetted, the ray failed, converted beyond the back of the sensor) in n_dropped.  This module holds the stamps' own host half:
+the launch's buffers, the renderer that keeps the sensor, and two small estimators; the rows, the launch base, the centre and the
+file layout are psf_probe's."""
 import ctypes as C
 import dataclasses
 import math
-import os
 
 import numpy as np
 
-from . import _abi, fits_io, psf_map
+from . import _abi, psf_probe
+from .psf_probe import summary_header        # noqa: F401  (psf_image.summary_header: the SUMMARY table's header)
 
 STAGES = {"psf": 1, "ops": 2, "sensor": 3}
+FLUX_STAGES = ("ops", "sensor")     # the stages that run the operator chain, whose photons must leave with equal flux
 UNITS = {"psf": "arcsec", "ops": "pixel", "sensor": "pixel"}
 MAX_SIZE = _abi.PSF_IMAGE_MAX
 IMAGE_REQ = ("file_name", "scale")
@@ -79,17 +81,12 @@ def check_scale(scale):
 
 
 def check_stage(stage):
-    if stage not in STAGES:
-        raise ValueError(f"psf_image: stage must be one of {sorted(STAGES)}, not {stage!r}")
+    psf_probe.check_stage("psf_image", stage, STAGES)
 
 
 def refuse_flux_operators(scene, stage):
     """The counts are unweighted: a chain whose photons leave with unequal flux cannot be binned"""
-    if stage != "psf":
-        for op in getattr(scene, "ops", None) or []:
-            if int(op[0]) == _abi.IMS_OP_BANDPASS_RATIO:
-                raise ValueError("psf_image: the photon-operator chain holds a BandpassRatio operator, whose photons carry unequal "
-                                 "flux; the stamp counts photons unweighted")
+    psf_probe.refuse_flux_operators("psf_image", "stamp", FLUX_STAGES, scene, stage)
 
 
 def require_sensor(scene, stage):
@@ -101,7 +98,7 @@ def renderer_for(scene, stage, seed=None, device="cuda:0"):
     """psf_map.renderer_for for stages "psf" and "ops"; for "sensor" the same bare one-pixel scene with the sensor's model and
     absorption table kept -- the conversion reads nothing else, so no pixel-boundary state of a CCD is made"""
     if stage != "sensor":
-        return psf_map.renderer_for(scene, seed, device)
+        return psf_probe.renderer_for(scene, seed, device)
     from .engine import Renderer, make_slots
     sensor = dataclasses.replace(scene.sensor, slots=make_slots([(1, 1, 1, 1)]), scratch_cells=0)
     bare = dataclasses.replace(scene, nx=1, ny=1, xmin=1, ymin=1, sensor=sensor, track_static_delta=0,
@@ -109,7 +106,7 @@ def renderer_for(scene, stage, seed=None, device="cuda:0"):
     return Renderer(bare, device)
 
 
-class Prepared:
+class Prepared(psf_probe.FieldPointLaunch):
     """The rows and the stamp of one launch resident on the device: call it to enqueue ims_psf_image, result() to fetch Stamps."""
 
     def __init__(self, renderer, rows, stage, size, scale, centre=None, inv_scale=None):
@@ -121,15 +118,7 @@ class Prepared:
         self.scale = check_scale(scale)
         # (inv_scale: an exact value for the device in place of the quotient formed here)
         self.inv_scale = 1.0 / self.scale if inv_scale is None else float(inv_scale)
-        self.renderer, self.stage, self.stage_name = r, STAGES[stage], stage
-        rows, self.obj_t, prefix, self.pre_t = r._upload_objects(rows)
-        self.n, self.n_segments = len(rows), int(prefix[-1])
-        self.photons = int(rows["n_phot"].sum())
-        from .engine import _seg_ptr
-        self.params = r.bound.params(self.obj_t.data_ptr(), self.n, self.pre_t.data_ptr(), self.n_segments, r.image.data_ptr(), None,
-                                     _seg_ptr(self.pre_t))
-        self.centre = None if centre is None else np.ascontiguousarray(centre, dtype=np.float64).reshape(self.n, 2)
-        self.centre_t = None if self.centre is None else torch.from_numpy(self.centre).to(r.device)
+        super().__init__(renderer, rows, stage, STAGES, centre)
         self.spec = _abi.PsfImage(self.nx, self.ny, self.inv_scale)
         self.counts = torch.zeros((max(self.n, 1), self.ny, self.nx), dtype=torch.int64, device=r.device)
         self.outside = torch.zeros(max(self.n, 1), dtype=torch.int64, device=r.device)
@@ -137,16 +126,13 @@ class Prepared:
 
     def __call__(self):
         r = self.renderer
-        _abi.check(r.lib.ims_psf_image(C.byref(self.params), self.stage, C.byref(self.spec),
-                                       None if self.centre_t is None else self.centre_t.data_ptr(), self.counts.data_ptr(),
+        _abi.check(r.lib.ims_psf_image(C.byref(self.params), self.stage, C.byref(self.spec), self.centre_ptr(), self.counts.data_ptr(),
                                        self.outside.data_ptr(), self.dropped.data_ptr(), r._stream()), "ims_psf_image")
 
     def result(self):
-        self.renderer.synchronize()
-        counts = self.counts.cpu().numpy()[:self.n]
-        return Stamps(counts=counts, n_used=counts.sum(axis=(1, 2)), n_outside=self.outside.cpu().numpy()[:self.n],
-                      n_dropped=self.dropped.cpu().numpy()[:self.n], scale=self.scale, inv_scale=self.inv_scale,
-                      stage=self.stage_name, centre=self.centre)
+        counts, outside, dropped = self.fetch(self.counts, self.outside, self.dropped)
+        return Stamps(counts=counts, n_used=counts.sum(axis=(1, 2)), n_outside=outside, n_dropped=dropped, scale=self.scale,
+                      inv_scale=self.inv_scale, stage=self.stage_name, centre=self.centre)
 
 
 def images(scene_or_psf, points, n_photons, size, scale, stage="psf", centre=None, wavelength=None, seed=None, device="cuda:0",
@@ -164,31 +150,17 @@ def images(scene_or_psf, points, n_photons, size, scale, stage="psf", centre=Non
     check_stage(stage)
     nx, ny = check_size(size)
     scale = check_scale(scale)
-    scene = psf_map._as_scene(scene_or_psf)
+    scene = psf_probe._as_scene(scene_or_psf)
     refuse_flux_operators(scene, stage)
     require_sensor(renderer.scene if renderer is not None else scene, stage)
     row_stage = "psf" if stage == "psf" else "ops"
-    if isinstance(points, np.ndarray) and points.dtype.names is not None:
-        rows = np.ascontiguousarray(points, dtype=_abi.OBJECT_DTYPE).copy()
-        if n_photons is not None:
-            rows["n_phot"] = np.broadcast_to(np.asarray(n_photons, dtype=np.int64), (len(rows),))
-    else:
-        if n_photons is None:
-            raise ValueError("psf_image: n_photons is required with pixel positions")
-        rows = psf_map.point_rows(scene, points, n_photons, row_stage, wavelength)
-    if isinstance(centre, str) and centre not in ("nominal", "centroid"):
-        raise ValueError(f"psf_image: centre must be 'nominal', 'centroid' or an [n][2] array, not {centre!r}")
+    rows = psf_probe.probe_rows("psf_image", scene, points, n_photons, row_stage, wavelength)
+    centre = psf_probe.resolve_centre("psf_image", centre)             # (a string is checked here, before anything ends the call)
     if len(rows) == 0:
         zeros = np.zeros(0, dtype=np.int64)
         return Stamps(np.zeros((0, ny, nx), dtype=np.int64), zeros, zeros, zeros, scale, 1.0 / scale, stage, None)
     r = renderer if renderer is not None else renderer_for(scene, stage, seed, device)
-    if isinstance(centre, str):
-        if centre == "centroid":
-            m = psf_map.compute(scene, rows, stage=row_stage, renderer=r)
-            centre = np.stack([m["xbar"], m["ybar"]], axis=1)        # (NaN where no photon arrived: that row has nothing to bin)
-        else:
-            centre = None
-    run = Prepared(r, rows, stage, (nx, ny), scale, centre)
+    run = Prepared(r, rows, stage, (nx, ny), scale, psf_probe.resolve_centre("psf_image", centre, scene, rows, row_stage, r))
     run()
     return run.result()
 
@@ -236,26 +208,9 @@ def parse_config(cfg, ev):
     centre: nominal | centroid}` -> the keywords of ccd_images.  size: an int or [nx, ny].  file_name and dir stay unevaluated:
     they may differ per CCD."""
     from .lsst_image import GalSimConfigError
-    if not isinstance(cfg, dict):
-        raise GalSimConfigError("output.psf_image must be a dict")
-    for k in cfg:
-        if k not in IMAGE_REQ and k not in IMAGE_OPT:
-            raise GalSimConfigError(f"Unexpected attribute {k} found in output.psf_image")
-    for k in IMAGE_REQ:
-        if k not in cfg:
-            raise GalSimConfigError(f"Attribute {k} is required in output.psf_image")
-    nx = int(ev.value(cfg.get("nx", 4)))
-    n_photons = int(ev.value(cfg.get("n_photons", 1000000)))
-    stage = str(ev.value(cfg.get("stage", "psf")))
+    kw = psf_probe.parse_head("psf_image", cfg, ev, IMAGE_REQ, IMAGE_OPT, nx=4, n_photons=1000000, stages=STAGES, centre=True)
     size = cfg.get("size", 64)
     size = [ev.value(v) for v in size] if isinstance(size, (list, tuple)) else ev.value(size)
-    centre = str(ev.value(cfg.get("centre", "nominal")))
-    if nx < 1:
-        raise GalSimConfigError("output.psf_image.nx must be at least 1")
-    if n_photons < 1:
-        raise GalSimConfigError("output.psf_image.n_photons must be at least 1")
-    if stage not in STAGES:
-        raise GalSimConfigError(f"output.psf_image.stage must be one of {sorted(STAGES)}, not {stage}")
     try:
         if isinstance(size, float) and size != int(size):
             raise ValueError(f"psf_image: size must be an int or (nx, ny), not {size!r}")
@@ -263,16 +218,13 @@ def parse_config(cfg, ev):
         scale = check_scale(ev.value(cfg["scale"]))
     except (TypeError, ValueError) as e:
         raise GalSimConfigError(f"output.{str(e).replace('psf_image: ', 'psf_image.', 1)}") from None
-    if centre not in ("nominal", "centroid"):
-        raise GalSimConfigError(f"output.psf_image.centre must be nominal or centroid, not {centre}")
-    return dict(nx=nx, n_photons=n_photons, stage=stage, size=size, scale=scale, centre=centre)
+    return dict(kw, size=size, scale=scale)
 
 
 def make_header(det_name, result, wavelength, n_photons, nx_ccd, ny_ccd, n, centre, sampled=False):
-    """the cards of psf_map's header that apply (the CCD, the stage, the wavelength, NPHOT and the grid of the points' pixel
-    positions: X_FIRST, X_STEP, Y_FIRST, Y_STEP, x fastest along axis 3), and the stamp: UNITS, SCALE, NX, NY, CENTRE"""
-    h = psf_map.make_header(det_name, result.stage, wavelength, n_photons, nx_ccd, ny_ccd, n, sampled)
-    h = {k: v for k, v in h.items() if not k.startswith("PLANE")}
+    """the probes' common cards (the CCD, the stage, the wavelength, NPHOT and the grid of the points' pixel positions: X_FIRST,
+    X_STEP, Y_FIRST, Y_STEP, x fastest along axis 3), and the stamp: UNITS, SCALE, NX, NY, CENTRE"""
+    h = psf_probe.probe_header(det_name, result.stage, wavelength, n_photons, nx_ccd, ny_ccd, n, sampled)
     h["stage"] = (str(result.stage), "psf: after the PSF; ops: + operators; sensor: + conversion")
     h["units"] = (UNITS[result.stage], "of SCALE")
     h["scale"] = (float(result.scale), "side of a cell; axis 1 is x, axis 2 is y")
@@ -281,10 +233,6 @@ def make_header(det_name, result, wavelength, n_photons, nx_ccd, ny_ccd, n, cent
     h["n_grid"] = (int(n), "points per CCD axis; axis 3 holds n_grid^2, x fastest")
     h["centre"] = (str(centre), "stamps centred on the nominal position or the centroid")
     return h
-
-
-def summary_header(det_name):
-    return {"det_name": (str(det_name), "CCD")}
 
 
 def summary(result, points):
@@ -298,19 +246,12 @@ def write(file_name, hdus):
     """hdus: [(cube, header, summary, summary header)] per CCD -> two HDUs each: the counts as an f64 image [point][ny][nx]
     (exact for counts, psf_profile's number format) and a binary table SUMMARY, one row per point, with the columns of SUMMARY
     (x, y as doubles, the three counts as 64-bit integers)"""
-    os.makedirs(os.path.dirname(file_name) or ".", exist_ok=True)
-    with open(file_name, "wb") as fobj:
-        for k, (cube, h, s, sh) in enumerate(hdus):
-            fobj.write(fits_io.hdu_bytes(dict(h), np.asarray(cube, dtype=np.float64), primary=(k == 0)))
-            s = np.asarray(s, dtype=np.float64).reshape(-1, len(SUMMARY))
-            cols = [(name, "K" if name.startswith("n_") else "D", s[:, j].astype(np.int64) if name.startswith("n_") else s[:, j])
-                    for j, name in enumerate(SUMMARY)]
-            fobj.write(fits_io.bintable_hdu_bytes(cols, header=dict(sh), extname="SUMMARY"))
+    psf_probe.write_counts(file_name, hdus, SUMMARY)
 
 
 def ccd_images(scene, det_name, nx, n_photons, stage, size, scale, centre="nominal", wavelength=None, wl_eff=None, device="cuda:0"):
     """The stamps of one CCD on psf_map's nx x nx grid over the scene's pixels: (cube, header, summary, summary header)"""
-    pts = psf_map.grid_points(scene.nx, scene.ny, nx)
+    pts = psf_probe.grid_points(scene.nx, scene.ny, nx)
     res = images(scene, pts, n_photons, size, scale, stage=stage, centre=centre, wavelength=wavelength, device=device)
     sampled = wavelength is None
     h = make_header(det_name, res, wl_eff if sampled else wavelength, n_photons, scene.nx, scene.ny, nx, centre, sampled)

@@ -3,21 +3,20 @@
 The photons of a point are the photons a render would shoot for it -- the PSF components of the scene (AtmosphericPSF with its
 second kick and optical screen, Gaussian, Kolmogorov, DoubleGaussian) and, in stage "ops", the photon-operator chain up to the
 position the sensor would receive -- but they are reduced on the GPU to six weighted sums and two counts per point instead of
-being landed or stored.  This module holds the host half: the point rows, the launch, and the moments formed from the sums.
+being landed or stored.  This module holds the moments' own host half: the two launches' buffers, and the moments formed from the
+sums; the point rows, the launch base and the common head of the config key are psf_probe's, shared with psf_profile and psf_image.
 
 Units: stage "psf" leaves the offsets as the PSF kicks make them, in arcsec (+u west, +v north: the rows' local WCS is the
 identity); stage "ops" gives focal-plane pixels of the scene's CCD relative to the point's pixel position."""
 import ctypes as C
-import dataclasses
 import math
 import os
 
 import numpy as np
 
-from . import _abi, fits_io
-from ._abi import OBJECT_DTYPE
+from . import _abi, fits_io, psf_probe
+from .psf_probe import STAGES, _as_scene, grid_points, point_rows, renderer_for        # noqa: F401  (psf_map.<name> is their public home)
 
-STAGES = {"psf": 1, "ops": 2}
 FWHM_PER_SIGMA = 2.3548200450309493
 MOMENTS_DTYPE = np.dtype([("flux", "<f8"), ("n_used", "<i8"), ("n_dropped", "<i8"), ("xbar", "<f8"), ("ybar", "<f8"),
                           ("Ixx", "<f8"), ("Iyy", "<f8"), ("Ixy", "<f8"), ("sigma", "<f8"), ("e1", "<f8"), ("e2", "<f8"),
@@ -68,69 +67,13 @@ def moments_from_sums(sums, counts):
     return out
 
 
-def _as_scene(scene_or_psf):
-    """a Scene as it is; a list of PSF component tuples becomes a scene of that PSF alone (stage "psf" only: no operators)"""
-    from . import configs
-    from .engine import Scene
-    if isinstance(scene_or_psf, Scene):
-        return scene_or_psf
-    r2, cdf = configs.standard_tables()
-    return Scene(nx=1, ny=1, psf=list(scene_or_psf), ops=[], radial_r2=r2, radial_cdf=cdf)
-
-
-def point_rows(scene, xy, n_photons, stage="psf", wavelength=None):
-    """Object rows for the pixel positions xy [n][2] of the scene's CCD: point sources of unit photon flux, point i on the random
-    stream of object id i.  With a WCS on the scene's optics the rows carry the field angle of their position (the atmosphere's
-    and the optical screen's `theta`) and, for stage "ops", the local WCS and the DCR angles a catalog object there would get;
-    without one the points are on axis.  wavelength [nm]: None samples the scene's first wavelength table."""
-    from . import configs
-    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
-    n = len(xy)
-    o = np.zeros(n, dtype=OBJECT_DTYPE)
-    o["obj_id"] = np.arange(n)
-    o["n_phot"] = np.broadcast_to(np.asarray(n_photons, dtype=np.int64), (n,))
-    if np.any(o["n_phot"] < 0):
-        raise ValueError("psf_map: negative photon count")
-    o["x0"], o["y0"] = xy[:, 0], xy[:, 1]
-    o["flux_per_photon"] = 1.0
-    o["prof_table"], o["bf_state"] = _abi.IMS_PROF_POINT, -1
-    o["jac"] = (1.0, 0.0, 0.0, 1.0)
-    o["winv"] = (1.0, 0.0, 0.0, 1.0)
-    lim = np.iinfo(np.int32)
-    o["stamp_xmin"], o["stamp_xmax"], o["stamp_ymin"], o["stamp_ymax"] = lim.min, lim.max, lim.min, lim.max
-    if wavelength is not None:
-        o["sed_table"], o["sed_wave"] = -1, float(wavelength)
-    elif scene.sed_tables is not None:
-        o["sed_table"] = 0
-    else:
-        raise ValueError("psf_map: the scene has no wavelength table: give `wavelength`")
-    optics = scene.optics
-    has_wcs = optics is not None and getattr(optics, "img_wcs", None) is not None and getattr(optics, "icrf_to_field", None) is not None
-    if has_wcs and n:
-        o["atm_tan_x"], o["atm_tan_y"] = configs.field_angles(scene, xy[:, 0], xy[:, 1])
-        if stage == "ops":
-            winv, p0 = configs.local_wcs_inverse(optics.img_wcs, xy[:, 0], xy[:, 1])
-            o["winv"] = winv
-            v = configs.VISIT
-            o["dcr_tanz"], o["dcr_sinp"], o["dcr_cosp"] = configs.dcr_angles(p0, math.radians(v["latitude"]), math.radians(v["hour_angle"]),
-                                                                             math.radians(v["ra"]))
-    return o
-
-
-class Prepared:
+class Prepared(psf_probe.FieldPointLaunch):
     """The rows of one launch resident on the device: call it to enqueue ims_psf_moments, result() to fetch the moments."""
 
     def __init__(self, renderer, rows, stage):
-        if stage not in STAGES:
-            raise ValueError(f"psf_map: stage must be one of {sorted(STAGES)}, not {stage!r}")
+        psf_probe.check_stage("psf_map", stage)
+        super().__init__(renderer, rows, stage)
         r, torch = renderer, renderer.torch
-        self.renderer, self.stage = r, STAGES[stage]
-        rows, self.obj_t, prefix, self.pre_t = r._upload_objects(rows)
-        self.n, self.n_segments = len(rows), int(prefix[-1])
-        self.photons = int(rows["n_phot"].sum())
-        from .engine import _seg_ptr
-        self.params = r.bound.params(self.obj_t.data_ptr(), self.n, self.pre_t.data_ptr(), self.n_segments, r.image.data_ptr(), None,
-                                     _seg_ptr(self.pre_t))
         self.partial = torch.empty(max(8 * self.n_segments, 1), dtype=torch.float64, device=r.device)
         self.sums = torch.zeros((max(self.n, 1), 6), dtype=torch.float64, device=r.device)
         self.counts = torch.zeros((max(self.n, 1), 2), dtype=torch.int64, device=r.device)
@@ -142,19 +85,10 @@ class Prepared:
 
     def raw(self):
         """(sums [n][6], counts [n][2]) on the host"""
-        self.renderer.synchronize()
-        return self.sums.cpu().numpy()[:self.n], self.counts.cpu().numpy()[:self.n]
+        return self.fetch(self.sums, self.counts)
 
     def result(self):
         return moments_from_sums(*self.raw())
-
-
-def renderer_for(scene, seed=None, device="cuda:0"):
-    """A renderer of the scene's PSF, operators and optics without its sensor (which neither stage reaches)"""
-    from .engine import Renderer
-    bare = dataclasses.replace(scene, nx=1, ny=1, xmin=1, ymin=1, sensor=None, track_static_delta=0,
-                               seed=scene.seed if seed is None else int(seed))
-    return Renderer(bare, device)
 
 
 def compute(scene_or_psf, points, n_photons=None, stage="psf", wavelength=None, seed=None, device="cuda:0", renderer=None):
@@ -166,17 +100,9 @@ def compute(scene_or_psf, points, n_photons=None, stage="psf", wavelength=None, 
     stage: "psf" -- shoot + PSF, offsets in arcsec; "ops" -- also the scene's photon operators, focal-plane pixels relative to
     the point.  seed: the random seed (default: the scene's).  A point all of whose photons are vignetted has n_used 0 and NaN
     moments.  The result does not depend on which other points share the call, nor on their order."""
-    if stage not in STAGES:
-        raise ValueError(f"psf_map: stage must be one of {sorted(STAGES)}, not {stage!r}")
+    psf_probe.check_stage("psf_map", stage)
     scene = _as_scene(scene_or_psf)
-    if isinstance(points, np.ndarray) and points.dtype.names is not None:
-        rows = np.ascontiguousarray(points, dtype=OBJECT_DTYPE).copy()
-        if n_photons is not None:
-            rows["n_phot"] = np.broadcast_to(np.asarray(n_photons, dtype=np.int64), (len(rows),))
-    else:
-        if n_photons is None:
-            raise ValueError("psf_map: n_photons is required with pixel positions")
-        rows = point_rows(scene, points, n_photons, stage, wavelength)
+    rows = psf_probe.probe_rows("psf_map", scene, points, n_photons, stage, wavelength)
     if len(rows) == 0:
         return np.zeros(0, dtype=MOMENTS_DTYPE)
     r = renderer if renderer is not None else renderer_for(scene, seed, device)
@@ -235,25 +161,20 @@ def adaptive_start(moments, guess_centre=None, guess_sigma=None):
     return state, status
 
 
-class PreparedAdaptive:
+class PreparedAdaptive(psf_probe.FieldPointLaunch):
     """The rows of one adaptive-moments run resident on the device, with the state the iteration starts from: call it to iterate
     (rounds are enqueued in batches of ADAPTIVE_ROUNDS, the statuses read between batches, until no row is running or max_iter
     rounds are done), result() to fetch the rows.  rounds(k) enqueues k rounds and reads nothing back."""
 
     def __init__(self, renderer, rows, stage, state, status, aux=None, tol=1e-6, max_iter=100):
-        if stage not in STAGES:
-            raise ValueError(f"psf_map: stage must be one of {sorted(STAGES)}, not {stage!r}")
+        psf_probe.check_stage("psf_map", stage)
         if not (tol > 0.0 and math.isfinite(tol)):
             raise ValueError("psf_map: tol must be positive and finite")
         if int(max_iter) < 1:
             raise ValueError("psf_map: max_iter must be at least 1")
+        super().__init__(renderer, rows, stage)
         r, torch = renderer, renderer.torch
-        self.renderer, self.stage, self.tol, self.max_iter, self.done = r, STAGES[stage], float(tol), int(max_iter), 0
-        rows, self.obj_t, prefix, self.pre_t = r._upload_objects(rows)
-        self.n, self.n_segments = len(rows), int(prefix[-1])
-        from .engine import _seg_ptr
-        self.params = r.bound.params(self.obj_t.data_ptr(), self.n, self.pre_t.data_ptr(), self.n_segments, r.image.data_ptr(), None,
-                                     _seg_ptr(self.pre_t))
+        self.tol, self.max_iter, self.done = float(tol), int(max_iter), 0
         n = self.n
         st2 = np.zeros((max(n, 1), 2), dtype=np.int32)
         st2[:n, 0] = np.asarray(status, dtype=np.int32).reshape(n)
@@ -285,9 +206,7 @@ class PreparedAdaptive:
 
     def raw(self):
         """(state [n][5], status [n][2], aux [n][4]) on the host"""
-        self.renderer.synchronize()
-        n = self.n
-        return self.state.cpu().numpy()[:n], self.status.cpu().numpy()[:n], self.aux.cpu().numpy()[:n]
+        return self.fetch(self.state, self.status, self.aux)
 
     def result(self):
         return adaptive_from_state(*self.raw())
@@ -313,17 +232,9 @@ def adaptive(scene_or_psf, points, n_photons=None, stage="psf", guess_centre=Non
     status: 0 converged; 1 max_iter reached; 2 failed (the weight stopped being positive definite, or the row has no usable start:
     a single photon without guess_sigma); 3 no photon arrived (NaN).  The result does not depend on which other points share the
     call, nor on their order."""
-    if stage not in STAGES:
-        raise ValueError(f"psf_map: stage must be one of {sorted(STAGES)}, not {stage!r}")
+    psf_probe.check_stage("psf_map", stage)
     scene = _as_scene(scene_or_psf)
-    if isinstance(points, np.ndarray) and points.dtype.names is not None:
-        rows = np.ascontiguousarray(points, dtype=OBJECT_DTYPE).copy()
-        if n_photons is not None:
-            rows["n_phot"] = np.broadcast_to(np.asarray(n_photons, dtype=np.int64), (len(rows),))
-    else:
-        if n_photons is None:
-            raise ValueError("psf_map: n_photons is required with pixel positions")
-        rows = point_rows(scene, points, n_photons, stage, wavelength)
+    rows = psf_probe.probe_rows("psf_map", scene, points, n_photons, stage, wavelength)
     if len(rows) == 0:
         return np.zeros(0, dtype=ADAPTIVE_DTYPE)
     r = renderer if renderer is not None else renderer_for(scene, seed, device)
@@ -343,23 +254,7 @@ def parse_config(cfg, ev):
     unevaluated: they may differ per CCD.  With `moments: adaptive` (default `unweighted`) the result also holds moments and
     the iteration's guess_sigma (None: the unweighted start), tolerance (1e-6) and max_iter (100)."""
     from .lsst_image import GalSimConfigError
-    if not isinstance(cfg, dict):
-        raise GalSimConfigError("output.psf_map must be a dict")
-    for k in cfg:
-        if k not in MAP_REQ and k not in MAP_OPT:
-            raise GalSimConfigError(f"Unexpected attribute {k} found in output.psf_map")
-    for k in MAP_REQ:
-        if k not in cfg:
-            raise GalSimConfigError(f"Attribute {k} is required in output.psf_map")
-    nx = int(ev.value(cfg.get("nx", 8)))
-    n_photons = int(ev.value(cfg.get("n_photons", 100000)))
-    stage = str(ev.value(cfg.get("stage", "psf")))
-    if nx < 1:
-        raise GalSimConfigError("output.psf_map.nx must be at least 1")
-    if n_photons < 1:
-        raise GalSimConfigError("output.psf_map.n_photons must be at least 1")
-    if stage not in STAGES:
-        raise GalSimConfigError(f"output.psf_map.stage must be one of {sorted(STAGES)}, not {stage}")
+    kw = psf_probe.parse_head("psf_map", cfg, ev, MAP_REQ, MAP_OPT, nx=8, n_photons=100000)
     moments = str(ev.value(cfg.get("moments", "unweighted")))
     if moments not in MOMENT_KINDS:
         raise GalSimConfigError(f"output.psf_map.moments must be one of {list(MOMENT_KINDS)}, not {moments}")
@@ -367,7 +262,7 @@ def parse_config(cfg, ev):
         for k in ADAPTIVE_KEYS:
             if k in cfg:
                 raise GalSimConfigError(f"output.psf_map.{k} is given without moments: adaptive")
-        return dict(nx=nx, n_photons=n_photons, stage=stage)
+        return kw
     guess_sigma = float(ev.value(cfg["guess_sigma"])) if "guess_sigma" in cfg else None
     tolerance = float(ev.value(cfg.get("tolerance", 1e-6)))
     max_iter = int(ev.value(cfg.get("max_iter", 100)))
@@ -377,17 +272,7 @@ def parse_config(cfg, ev):
         raise GalSimConfigError("output.psf_map.tolerance must be positive and finite")
     if max_iter < 1:
         raise GalSimConfigError("output.psf_map.max_iter must be at least 1")
-    return dict(nx=nx, n_photons=n_photons, stage=stage, moments=moments, guess_sigma=guess_sigma, tolerance=tolerance,
-                max_iter=max_iter)
-
-
-def grid_points(nx_ccd, ny_ccd, n):
-    """n x n pixel positions over a CCD of nx_ccd x ny_ccd pixels (pixel centres 1 .. nx_ccd): the centres of n x n equal
-    cells, x fastest -> [n * n][2]"""
-    gx = 0.5 + (np.arange(n) + 0.5) * (nx_ccd / n)
-    gy = 0.5 + (np.arange(n) + 0.5) * (ny_ccd / n)
-    X, Y = np.meshgrid(gx, gy)
-    return np.stack([X.ravel(), Y.ravel()], axis=1)
+    return dict(kw, moments=moments, guess_sigma=guess_sigma, tolerance=tolerance, max_iter=max_iter)
 
 
 def cube(moments, n):
@@ -403,12 +288,7 @@ def adaptive_cube(rows, n):
 def make_header(det_name, stage, wavelength, n_photons, nx_ccd, ny_ccd, n, sampled=False, adaptive=None):
     """wavelength [nm]: the photons' one wavelength, or with sampled the effective wavelength of the bandpass they sample.
     adaptive: None, or (tolerance, max_iter) of a cube that carries the ADAPTIVE_PLANES behind the PLANES"""
-    h = {"det_name": (str(det_name), "CCD"), "stage": (str(stage), "psf: arcsec after the PSF; ops: pixels after the operators"),
-         "units": ("arcsec" if stage == "psf" else "pixel", "of the centroids; squared for the moments"),
-         "wavelen": (float(wavelength), "(nm) effective; photons sample the bandpass" if sampled else "(nm) of every photon"),
-         "nphot": (int(n_photons), "photons per point"),
-         "x_first": (float(0.5 + 0.5 * nx_ccd / n), "CCD pixel x of the first column"), "x_step": (float(nx_ccd / n), "pixels per column"),
-         "y_first": (float(0.5 + 0.5 * ny_ccd / n), "CCD pixel y of the first row"), "y_step": (float(ny_ccd / n), "pixels per row")}
+    h = psf_probe.probe_header(det_name, stage, wavelength, n_photons, nx_ccd, ny_ccd, n, sampled)
     for k, (name, comment) in enumerate(PLANES, 1):
         h[f"PLANE{k}"] = (name, comment)
     if adaptive is not None:

@@ -3,8 +3,9 @@
 The photons of a point are those of psf_map (ims_psf_moments): what a render would shoot for it, in stage "psf" after the PSF
 components [arcsec], in stage "ops" after the photon-operator chain [pixels relative to the point].  Here they are reduced on the
 GPU to counts in radial bins and azimuthal sectors instead of to second moments: the faint `1/r^2` halo, the diffraction spikes
-and the encircled-energy radii, none of which the second moments see.  This module holds the host half: the edges and sector
-directions, the launch, and the estimators formed from the counts.
+and the encircled-energy radii, none of which the second moments see.  This module holds the profile's own host half: the edges
+and sector directions, the launch's buffers, and the estimators formed from the counts; the rows, the launch base, the centre and
+the file layout are psf_probe's.
 
 Layout of the counts of a point, [n_r + 2][n_phi + 1]: radial index 0 holds the photons inside the first edge, 1 .. n_r the bins
 [r_{i-1}, r_i), n_r + 1 the photons at or beyond the last edge; sector b is the wedge from direction phi0 + 2 pi b / n_phi
@@ -12,13 +13,13 @@ counter-clockwise to the next, the last column the photons no sector claims (on 
 import ctypes as C
 import dataclasses
 import math
-import os
 
 import numpy as np
 
-from . import _abi, fits_io, psf_map
-from .psf_map import STAGES
+from . import _abi, psf_probe
+from .psf_probe import STAGES, summary_header        # noqa: F401  (psf_profile.summary_header: the SUMMARY table's header)
 
+FLUX_STAGES = ("ops",)              # the stages that run the operator chain, whose photons must leave with equal flux
 MAX_R, MAX_PHI = 64, 64
 PROFILE_REQ = ("file_name", "r_min", "r_max")
 PROFILE_OPT = ("dir", "nx", "n_photons", "stage", "n_r", "spacing", "n_phi", "phi0", "centre")
@@ -69,19 +70,14 @@ def sector_dirs(n_phi, phi0=0.0):
 
 def refuse_flux_operators(scene, stage):
     """The counts are unweighted: a chain whose photons leave with unequal flux cannot be histogrammed"""
-    if stage == "ops":
-        for op in getattr(scene, "ops", None) or []:
-            if int(op[0]) == _abi.IMS_OP_BANDPASS_RATIO:
-                raise ValueError("psf_profile: the photon-operator chain holds a BandpassRatio operator, whose photons carry unequal "
-                                 "flux; the profile counts photons unweighted")
+    psf_probe.refuse_flux_operators("psf_profile", "profile", FLUX_STAGES, scene, stage)
 
 
-class Prepared:
+class Prepared(psf_probe.FieldPointLaunch):
     """The rows and bins of one launch resident on the device: call it to enqueue ims_psf_profile, result() to fetch a Profile."""
 
     def __init__(self, renderer, rows, stage, r_edges, n_phi=0, phi0=0.0, centre=None, dirs=None, r2_edges=None):
-        if stage not in STAGES:
-            raise ValueError(f"psf_profile: stage must be one of {sorted(STAGES)}, not {stage!r}")
+        psf_probe.check_stage("psf_profile", stage)
         r, torch = renderer, renderer.torch
         refuse_flux_operators(r.scene, stage)
         self.r_edges, n_phi = check_bins(r_edges, n_phi if dirs is None else len(dirs))
@@ -90,32 +86,22 @@ class Prepared:
         if len(self.r2_edges) != len(self.r_edges) or not np.all(np.diff(self.r2_edges) > 0.0):
             raise ValueError("psf_profile: r2_edges must be strictly ascending, one per radius")
         self.dirs = sector_dirs(n_phi, phi0) if dirs is None else np.array(dirs, dtype=np.float64).reshape(n_phi, 2)
-        self.phi0, self.stage_name = float(phi0), stage
-        self.renderer, self.stage = r, STAGES[stage]
-        rows, self.obj_t, prefix, self.pre_t = r._upload_objects(rows)
-        self.n, self.n_segments = len(rows), int(prefix[-1])
-        self.photons = int(rows["n_phot"].sum())
-        from .engine import _seg_ptr
-        self.params = r.bound.params(self.obj_t.data_ptr(), self.n, self.pre_t.data_ptr(), self.n_segments, r.image.data_ptr(), None,
-                                     _seg_ptr(self.pre_t))
+        self.phi0 = float(phi0)
+        super().__init__(renderer, rows, stage, centre=centre)
         self.edge_t = torch.from_numpy(self.r2_edges).to(r.device)
         self.dir_t = torch.from_numpy(np.ascontiguousarray(self.dirs)).to(r.device) if n_phi else None
-        self.centre = None if centre is None else np.ascontiguousarray(centre, dtype=np.float64).reshape(self.n, 2)
-        self.centre_t = None if self.centre is None else torch.from_numpy(self.centre).to(r.device)
         self.spec = _abi.PsfProfile(len(self.r_edges) - 1, n_phi, self.edge_t.data_ptr(), self.dir_t.data_ptr() if n_phi else None)
         self.counts = torch.zeros((max(self.n, 1), len(self.r_edges) + 1, n_phi + 1), dtype=torch.int64, device=r.device)
         self.dropped = torch.zeros(max(self.n, 1), dtype=torch.int64, device=r.device)
 
     def __call__(self):
         r = self.renderer
-        _abi.check(r.lib.ims_psf_profile(C.byref(self.params), self.stage, C.byref(self.spec),
-                                         None if self.centre_t is None else self.centre_t.data_ptr(), self.counts.data_ptr(),
+        _abi.check(r.lib.ims_psf_profile(C.byref(self.params), self.stage, C.byref(self.spec), self.centre_ptr(), self.counts.data_ptr(),
                                          self.dropped.data_ptr(), r._stream()), "ims_psf_profile")
 
     def result(self):
-        self.renderer.synchronize()
-        counts = self.counts.cpu().numpy()[:self.n]
-        return Profile(counts=counts, n_used=counts.sum(axis=(1, 2)), n_dropped=self.dropped.cpu().numpy()[:self.n],
+        counts, dropped = self.fetch(self.counts, self.dropped)
+        return Profile(counts=counts, n_used=counts.sum(axis=(1, 2)), n_dropped=dropped,
                        r_edges=self.r_edges, r2_edges=self.r2_edges, dirs=self.dirs, phi0=self.phi0, stage=self.stage_name,
                        centre=self.centre)
 
@@ -130,33 +116,18 @@ def profile(scene_or_psf, points, n_photons, r_edges, n_phi=0, phi0=0.0, centre=
     nominal position; "centroid" -- from the centroid psf_map.compute measures for the same rows; an [n][2] array -- from
     nominal + centre.  A chain with a BandpassRatio operator is refused in stage "ops" (ValueError): the counts are unweighted.
     The counts of a point depend on nothing but the point: not on the other points of the call, their order, or the launch."""
-    if stage not in STAGES:
-        raise ValueError(f"psf_profile: stage must be one of {sorted(STAGES)}, not {stage!r}")
+    psf_probe.check_stage("psf_profile", stage)
     r_edges, n_phi = check_bins(r_edges, n_phi)
-    scene = psf_map._as_scene(scene_or_psf)
+    scene = psf_probe._as_scene(scene_or_psf)
     refuse_flux_operators(scene, stage)
-    if isinstance(points, np.ndarray) and points.dtype.names is not None:
-        rows = np.ascontiguousarray(points, dtype=_abi.OBJECT_DTYPE).copy()
-        if n_photons is not None:
-            rows["n_phot"] = np.broadcast_to(np.asarray(n_photons, dtype=np.int64), (len(rows),))
-    else:
-        if n_photons is None:
-            raise ValueError("psf_profile: n_photons is required with pixel positions")
-        rows = psf_map.point_rows(scene, points, n_photons, stage, wavelength)
+    rows = psf_probe.probe_rows("psf_profile", scene, points, n_photons, stage, wavelength)
+    centre = psf_probe.resolve_centre("psf_profile", centre)           # (a string is checked here, before anything ends the call)
     if len(rows) == 0:
         zeros = np.zeros(0, dtype=np.int64)
         return Profile(np.zeros((0, len(r_edges) + 1, n_phi + 1), dtype=np.int64), zeros, zeros, r_edges, r_edges * r_edges,
                        sector_dirs(n_phi, phi0), float(phi0), stage, None)
-    r = renderer if renderer is not None else psf_map.renderer_for(scene, seed, device)
-    if isinstance(centre, str):
-        if centre == "centroid":
-            m = psf_map.compute(scene, rows, stage=stage, renderer=r)
-            centre = np.stack([m["xbar"], m["ybar"]], axis=1)        # (NaN where no photon arrived: that row has nothing to bin)
-        elif centre == "nominal":
-            centre = None
-        else:
-            raise ValueError(f"psf_profile: centre must be 'nominal', 'centroid' or an [n][2] array, not {centre!r}")
-    run = Prepared(r, rows, stage, r_edges, n_phi, phi0, centre)
+    r = renderer if renderer is not None else psf_probe.renderer_for(scene, seed, device)
+    run = Prepared(r, rows, stage, r_edges, n_phi, phi0, psf_probe.resolve_centre("psf_profile", centre, scene, rows, stage, r))
     run()
     return run.result()
 
@@ -234,27 +205,11 @@ def parse_config(cfg, ev):
     n_phi: 0, phi0: 0 deg, centre: nominal | centroid}` -> the keywords of ccd_profile.  file_name and dir stay unevaluated: they
     may differ per CCD."""
     from .lsst_image import GalSimConfigError
-    if not isinstance(cfg, dict):
-        raise GalSimConfigError("output.psf_profile must be a dict")
-    for k in cfg:
-        if k not in PROFILE_REQ and k not in PROFILE_OPT:
-            raise GalSimConfigError(f"Unexpected attribute {k} found in output.psf_profile")
-    for k in PROFILE_REQ:
-        if k not in cfg:
-            raise GalSimConfigError(f"Attribute {k} is required in output.psf_profile")
-    nx = int(ev.value(cfg.get("nx", 4)))
-    n_photons = int(ev.value(cfg.get("n_photons", 1000000)))
-    stage = str(ev.value(cfg.get("stage", "psf")))
+    kw = psf_probe.parse_head("psf_profile", cfg, ev, PROFILE_REQ, PROFILE_OPT, nx=4, n_photons=1000000, centre=True)
     n_r, n_phi = int(ev.value(cfg.get("n_r", 32))), int(ev.value(cfg.get("n_phi", 0)))
     r_min, r_max = float(ev.value(cfg["r_min"])), float(ev.value(cfg["r_max"]))
-    spacing, centre = str(ev.value(cfg.get("spacing", "log"))), str(ev.value(cfg.get("centre", "nominal")))
+    spacing = str(ev.value(cfg.get("spacing", "log")))
     phi0 = ev.value(cfg.get("phi0", "0 deg"))
-    if nx < 1:
-        raise GalSimConfigError("output.psf_profile.nx must be at least 1")
-    if n_photons < 1:
-        raise GalSimConfigError("output.psf_profile.n_photons must be at least 1")
-    if stage not in STAGES:
-        raise GalSimConfigError(f"output.psf_profile.stage must be one of {sorted(STAGES)}, not {stage}")
     if not 1 <= n_r <= MAX_R:
         raise GalSimConfigError(f"output.psf_profile.n_r must be 1 .. {MAX_R}, not {n_r}")
     if n_phi != 0 and not 3 <= n_phi <= MAX_PHI:
@@ -267,12 +222,9 @@ def parse_config(cfg, ev):
         raise GalSimConfigError(f"output.psf_profile.r_min must be below r_max ({r_min} >= {r_max})")
     if spacing == "log" and r_min <= 0.0:
         raise GalSimConfigError("output.psf_profile.r_min must be positive with spacing: log")
-    if centre not in ("nominal", "centroid"):
-        raise GalSimConfigError(f"output.psf_profile.centre must be nominal or centroid, not {centre}")
     if isinstance(phi0, bool) or not isinstance(phi0, (int, float)):
         raise GalSimConfigError(f"output.psf_profile.phi0: cannot read {cfg.get('phi0')!r} as an angle")
-    return dict(nx=nx, n_photons=n_photons, stage=stage, r_edges=radial_edges(r_min, r_max, n_r, spacing), n_phi=n_phi, phi0=float(phi0),
-                centre=centre)
+    return dict(kw, r_edges=radial_edges(r_min, r_max, n_r, spacing), n_phi=n_phi, phi0=float(phi0))
 
 
 def check_scene(scene, stage):
@@ -293,9 +245,8 @@ def radial_edges(r_min, r_max, n_r, spacing="log"):
 
 
 def make_header(det_name, result, wavelength, n_photons, nx_ccd, ny_ccd, n, centre, sampled=False):
-    """the cards of psf_map's header that apply, and the bins: the edges as radii R_EDGE0 .. R_EDGE<n_r>"""
-    h = psf_map.make_header(det_name, result.stage, wavelength, n_photons, nx_ccd, ny_ccd, n, sampled)
-    h = {k: v for k, v in h.items() if not k.startswith("PLANE")}
+    """the probes' common cards, and the bins: the edges as radii R_EDGE0 .. R_EDGE<n_r>"""
+    h = psf_probe.probe_header(det_name, result.stage, wavelength, n_photons, nx_ccd, ny_ccd, n, sampled)
     h["units"] = ("arcsec" if result.stage == "psf" else "pixel", "of the radial edges")
     h["n_r"] = (int(result.n_r), "radial bins; axis 2 holds n_r + 2: under, bins, over")
     h["n_phi"] = (int(result.n_phi), "sectors; axis 1 holds n_phi + 1: the last unassigned")
@@ -306,28 +257,17 @@ def make_header(det_name, result, wavelength, n_photons, nx_ccd, ny_ccd, n, cent
     return h
 
 
-def summary_header(det_name):
-    return {"det_name": (str(det_name), "CCD")}
-
-
 def write(file_name, hdus):
     """hdus: [(cube, header, summary, summary header)] per CCD -> two HDUs each: the counts as an f64 image
     [point][radial][sector] (exact for counts) and a binary table SUMMARY, one row per point, with the columns of SUMMARY
     (n_used, n_dropped as 64-bit integers, the EE radii as doubles)"""
-    os.makedirs(os.path.dirname(file_name) or ".", exist_ok=True)
-    with open(file_name, "wb") as fobj:
-        for k, (cube, h, s, sh) in enumerate(hdus):
-            fobj.write(fits_io.hdu_bytes(dict(h), np.asarray(cube, dtype=np.float64), primary=(k == 0)))
-            s = np.asarray(s, dtype=np.float64).reshape(-1, len(SUMMARY))
-            cols = [(name, "K" if name.startswith("n_") else "D", s[:, j].astype(np.int64) if name.startswith("n_") else s[:, j])
-                    for j, name in enumerate(SUMMARY)]
-            fobj.write(fits_io.bintable_hdu_bytes(cols, header=dict(sh), extname="SUMMARY"))
+    psf_probe.write_counts(file_name, hdus, SUMMARY)
 
 
 def ccd_profile(scene, det_name, nx, n_photons, stage, r_edges, n_phi=0, phi0=0.0, centre="nominal", wavelength=None, wl_eff=None,
                 device="cuda:0"):
     """The profiles of one CCD on psf_map's nx x nx grid over the scene's pixels: (cube, header, summary, summary header)"""
-    pts = psf_map.grid_points(scene.nx, scene.ny, nx)
+    pts = psf_probe.grid_points(scene.nx, scene.ny, nx)
     res = profile(scene, pts, n_photons, r_edges, n_phi=n_phi, phi0=phi0, centre=centre, stage=stage, wavelength=wavelength, device=device)
     sampled = wavelength is None
     h = make_header(det_name, res, wl_eff if sampled else wavelength, n_photons, scene.nx, scene.ny, nx, centre, sampled)
