@@ -23,7 +23,8 @@ static ims_tuning_t tuning_defaults()
 
 // ---------------- process-wide mutable host state ----------------
 // The host objects of the library that outlive a call.  Those at namespace scope are declared here, with what guards them.
-// Six stay function-local, where they are initialised at first use (and, for `rings`, where their element type is):
+// Six stay function-local, where they are initialised at first use (and, for `rings`, where their element type is) -- the two
+// plan functions in ims_plan_run.h, fft_inverse_impl in ims_fft_branch.h:
 //   plan_event: `evs`, the library events of RECORD / WAIT items by number                      -- under g_state_mutex
 //   ims_plans_run_joint: `rings`, per device the ring of joint tables and its cursor            -- under g_state_mutex: the choice
 //     of an entry and its `busy` flag (set there, cleared by the call's Undo under the lock again); the entry's buffers are
@@ -53,7 +54,7 @@ static std::mutex g_state_mutex;
 struct MarginBuf { double* list = nullptr; int32_t* count = nullptr; unsigned char* wave_count = nullptr; int64_t waves_cap = 0; uint32_t cap = 0; };
 static std::map<std::pair<int, void*>, MarginBuf> g_margin;      // under g_state_mutex (ims_shoot_accumulate)
 
-// the hipFFT plans per (size, transforms per plan, stream), under g_fft_mutex (imsim_hip.hip: fft_plan_get)
+// the hipFFT plans per (size, transforms per plan, stream), under g_fft_mutex (ims_fft_branch.h: fft_plan_get)
 static std::mutex g_fft_mutex;
 static std::map<std::tuple<int32_t, int64_t, void*>, hipfftHandle> g_fft_plans;
 

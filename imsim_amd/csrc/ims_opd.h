@@ -15,6 +15,9 @@
 //   k_opd_zk_final     per (field, entry): the chunks' partials summed in chunk order
 // Every sum has a fixed shape (a workgroup's tree over its 256 threads, then the partials in index order), so the results depend
 // neither on the launch geometry nor on which other fields share the call.
+//
+// A section of the one translation unit (imsim_hip.hip): the kernels in namespace ims, then the host side -- opd_run,
+// trace_field_points_run; entry points ims_opd, ims_opd_perturbed, ims_trace_field_points, ims_trace_field_points_perturbed.
 #pragma once
 #include "ims_photon.h"
 
@@ -378,3 +381,88 @@ __global__ __launch_bounds__(256) void k_trace_field_points(const ims_optics_t* 
 }
 
 }  // namespace ims
+
+extern "C" {
+
+static int opd_run(const ims_opd_t* P, const ims_optics_t* optics_dev, bool pert, void* stream)
+{
+    if (!P || !optics_dev) return set_err(IMS_ERR_ARG, "opd / optics is NULL");
+    if (P->n_fields < 0) return set_err(IMS_ERR_ARG, "opd: negative n_fields");
+    if (P->nx < 1 || P->nx > IMS_OPD_MAX_NX) return set_err(IMS_ERR_ARG, "opd: nx out of range");
+    if (P->reference != IMS_OPD_REF_CHIEF && P->reference != IMS_OPD_REF_MEAN) return set_err(IMS_ERR_ARG, "opd: unknown reference");
+    if (P->jmax < 0 || P->jmax > IMS_OPD_MAX_J) return set_err(IMS_ERR_ARG, "opd: jmax out of range (0 .. 66)");
+    if (!(P->dx > 0.0) || !(P->wavelength > 0.0) || !(P->sphere_radius > 0.0))
+        return set_err(IMS_ERR_ARG, "opd: dx, wavelength and sphere_radius must be positive");
+    if (P->n_fields == 0) return IMS_OK;
+    if (!P->dirs || !P->opd || !P->scratch) return set_err(IMS_ERR_ARG, "opd: dirs / opd / scratch is NULL");
+    if (P->jmax > 0) {
+        if (!P->zk_poly || !P->zk_m || !P->zk_ata || !P->zk_atw) return set_err(IMS_ERR_ARG, "opd: Zernike table or output is NULL");
+        if (!(P->r_outer > 0.0) || !(P->eps >= 0.0 && P->eps < 1.0)) return set_err(IMS_ERR_ARG, "opd: r_outer > 0 and 0 <= eps < 1");
+    }
+    const OpdLayout L = opd_layout(*P);
+    if ((L.n_rays + OPD_WG - 1) / OPD_WG > 0x7fffffffLL || L.nblk > 0x7fffffffLL || P->n_fields > 65535)
+        return set_err(IMS_ERR_ARG, "opd: too many rays or fields for one call");
+    hipStream_t s = (hipStream_t)stream;
+    const ims_opd_t A = *P;
+    const dim3 per_block((unsigned)L.nblk, (unsigned)P->n_fields);
+    if (pert) hipLaunchKernelGGL((k_opd_trace<true>), dim3((unsigned)((L.n_rays + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, optics_dev, L);
+    else hipLaunchKernelGGL((k_opd_trace<false>), dim3((unsigned)((L.n_rays + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, optics_dev, L);
+    if (P->reference == IMS_OPD_REF_MEAN) hipLaunchKernelGGL(k_opd_hit_partial, per_block, dim3(OPD_WG), 0, s, A, L);
+    hipLaunchKernelGGL(k_opd_field, dim3((unsigned)P->n_fields), dim3(OPD_WG), 0, s, A, L, 0);
+    hipLaunchKernelGGL(k_opd_sphere, per_block, dim3(OPD_WG), 0, s, A, L);
+    hipLaunchKernelGGL(k_opd_field, dim3((unsigned)P->n_fields), dim3(OPD_WG), 0, s, A, L, 1);
+    const int64_t n_map = (int64_t)P->n_fields * L.npix;
+    hipLaunchKernelGGL(k_opd_map, dim3((unsigned)((n_map + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, L);
+    if (P->jmax > 0) {
+        hipLaunchKernelGGL(k_opd_zk_normal, dim3((unsigned)L.nchunk, (unsigned)P->n_fields), dim3(OPD_WG), 0, s, A, L);
+        const int64_t n_ent = (int64_t)P->n_fields * L.nent;
+        hipLaunchKernelGGL(k_opd_zk_final, dim3((unsigned)((n_ent + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, L);
+    }
+    HIP_TRY(hipGetLastError());
+    return IMS_OK;
+}
+
+int ims_opd(const ims_opd_t* P, const ims_optics_t* optics_dev, void* stream)
+{
+    return opd_run(P, optics_dev, false, stream);
+}
+
+int ims_opd_perturbed(const ims_opd_t* P, const ims_optics_perturbed_t* optics_dev, void* stream)
+{
+    return opd_run(P, optics_dev ? &optics_dev->optics : nullptr, true, stream);
+}
+
+static int trace_field_points_run(const ims_optics_t* optics_dev, bool pert, const double* thx, const double* thy, int64_t n,
+                                  double wave_nm, const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out,
+                                  void* stream)
+{
+    if (n < 0) return set_err(IMS_ERR_ARG, "trace_field_points: negative n");
+    if (n == 0) return IMS_OK;
+    if (!optics_dev || !thx || !thy || !pupil_xy || !xy_out || !ngood_out) return set_err(IMS_ERR_ARG, "trace_field_points: NULL argument");
+    if (n > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "trace_field_points: too many field points for one call");
+    if (n_rays < 1 || n_rays > IMS_TRACE_MAX_RAYS) return set_err(IMS_ERR_ARG, "trace_field_points: n_rays out of range");
+    if (!(wave_nm > 0.0)) return set_err(IMS_ERR_ARG, "trace_field_points: the wavelength must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    if (pert) hipLaunchKernelGGL((k_trace_field_points<true>), dim3((unsigned)n), dim3(OPD_WG), 0, s, optics_dev, thx, thy, wave_nm,
+                                 pupil_xy, (int)n_rays, xy_out, ngood_out);
+    else hipLaunchKernelGGL((k_trace_field_points<false>), dim3((unsigned)n), dim3(OPD_WG), 0, s, optics_dev, thx, thy, wave_nm,
+                            pupil_xy, (int)n_rays, xy_out, ngood_out);
+    HIP_TRY(hipGetLastError());
+    return IMS_OK;
+}
+
+int ims_trace_field_points(const ims_optics_t* optics_dev, const double* thx, const double* thy, int64_t n, double wave_nm,
+                           const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out, void* stream)
+{
+    return trace_field_points_run(optics_dev, false, thx, thy, n, wave_nm, pupil_xy, n_rays, xy_out, ngood_out, stream);
+}
+
+int ims_trace_field_points_perturbed(const ims_optics_perturbed_t* optics_dev, const double* thx, const double* thy, int64_t n,
+                                     double wave_nm, const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out,
+                                     void* stream)
+{
+    return trace_field_points_run(optics_dev ? &optics_dev->optics : nullptr, true, thx, thy, n, wave_nm, pupil_xy, n_rays, xy_out,
+                                  ngood_out, stream);
+}
+
+}  // extern "C"

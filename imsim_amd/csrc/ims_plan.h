@@ -6,7 +6,7 @@
 // _compile_plan), restated as one native pass so that a CCD of a focal plane costs the host a fraction of a millisecond
 // instead of five.  The Python planner stays as the checker (tests/test_device_table.py, tests/test_parity_gpu.py).
 //
-// A section of the one translation unit: imsim_hip.hip includes it at file scope, between two of its extern "C" blocks, ahead
+// A section of the one translation unit: ims_plan_run.h includes it at file scope, between its two extern "C" blocks, ahead
 // of the ims_plan_* entry points.  Uses the error helpers of ims_host.h; ims_run_plan and ims_gather_rows run what it builds.
 #pragma once
 

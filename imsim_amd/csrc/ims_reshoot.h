@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void k_reshoot_count(const ims_fft_object_t* _
     __shared__ long long part[4];
     const int64_t t = blockIdx.x;
     const int64_t first = t * RS_TILE;
-    const int64_t oi = find_prefix(r_prefix, n_objects, first);
+    const int64_t oi = find_object(r_prefix, n_objects, first);
     const ims_fft_object_t& o = objs[oi];
     const int64_t base = first - r_prefix[oi] + 4 * (int64_t)threadIdx.x;
     long long n = 0;
@@ -131,11 +131,11 @@ __global__ __launch_bounds__(256, (CHAIN == 1) ? IMS_CHAIN_WAVES : IMS_FUSED_WAV
     for (int64_t run = blockIdx.x; run < n_runs; run += gridDim.x) {
         int64_t g = run * RS_RUN;
         const int64_t g1 = g + RS_RUN < total ? g + RS_RUN : total;
-        int64_t t = find_prefix(scan, n_tiles, g);          // scan[t] <= g < scan[t + 1]
+        int64_t t = find_object(scan, n_tiles, g);          // scan[t] <= g < scan[t + 1]
         int64_t oi = -1, o_end = 0;
         while (g < g1) {
             const int64_t first = t * RS_TILE;
-            if (first >= o_end) { oi = find_prefix(r_prefix, n_objects, first); o_end = r_prefix[oi + 1]; }
+            if (first >= o_end) { oi = find_object(r_prefix, n_objects, first); o_end = r_prefix[oi + 1]; }
             const ims_fft_object_t& fo = fobjs[oi];
             const ims_object_t& po = pobjs[oi];
             const int64_t o_begin = r_prefix[oi];
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256, (CHAIN == 1) ? IMS_CHAIN_WAVES : IMS_FUSED_WAV
             g = gb;
             if (g < g1) {
                 ++t;
-                if (scan[t + 1] <= g) t = find_prefix(scan, n_tiles, g);     // empty tiles in between
+                if (scan[t + 1] <= g) t = find_object(scan, n_tiles, g);     // empty tiles in between
             }
         }
     }

@@ -15,6 +15,8 @@
 //   5. inversion lanes stride the n_pts abscissae u_j = j / (n_pts - 1): two bisections in LDS and one linear interpolation
 // The CDF is non-decreasing by construction (fl(P + r) is monotone in r, and the last entry of lane l is fl(P[l] + S[l]) =
 // P[l + 1]), and equal wherever the density is zero on both sides.
+//
+// A section of the one translation unit (imsim_hip.hip): the kernel in namespace ims, then its entry point ims_object_spectra.
 #pragma once
 #include "ims_math.h"
 
@@ -164,3 +166,38 @@ __global__ __launch_bounds__(64 * SED_WAVES) void k_object_spectra(const SedArgs
 }
 
 }  // namespace ims
+
+extern "C" {
+
+int ims_object_spectra(const double* grid, const double* thr, const double* ext_a, const double* ext_b, int32_t n_grid, double band_hi,
+                       const double* sed_wave, const double* sed_fphotons, const int64_t* sed_offset, int32_t n_sed,
+                       const int32_t* sed_id, const double* redshift, const double* mw_av, const double* mw_rv, int64_t n_obj,
+                       int32_t n_pts, double* flux, double* tables, int64_t row_offset, void* stream)
+{
+    if (n_obj < 0 || row_offset < 0) return set_err(IMS_ERR_ARG, "object spectra: negative object count or row offset");
+    if (n_obj == 0) return IMS_OK;
+    if (!grid || !thr || !ext_a || !ext_b || !sed_offset || !sed_id || !redshift || !mw_av || !mw_rv || !flux || !tables)
+        return set_err(IMS_ERR_ARG, "object spectra: an array is NULL");
+    if (n_sed < 0 || (n_sed > 0 && (!sed_wave || !sed_fphotons))) return set_err(IMS_ERR_ARG, "object spectra: the SED library is NULL");
+    if (n_grid < 2 || n_pts < 2) return set_err(IMS_ERR_ARG, "object spectra: the band grid and the tables need two points at least");
+    if ((int64_t)n_grid * SED_WAVES * (int64_t)sizeof(double) > SED_MAX_LDS) {
+        snprintf(g_err, sizeof(g_err), "object spectra: a band grid of %d points does not fit the %d doubles of LDS a wavefront has "
+                 "(a coarser step or a narrower band)", (int)n_grid, (int)(SED_MAX_LDS / (SED_WAVES * sizeof(double))));
+        return IMS_ERR_UNSUPPORTED;
+    }
+    const int64_t blocks = (n_obj + SED_WAVES - 1) / SED_WAVES;
+    if (blocks > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "object spectra: too many objects for one launch");
+    SedArgs A;
+    A.grid = grid; A.thr = thr; A.ext_a = ext_a; A.ext_b = ext_b;
+    A.wave = sed_wave; A.fphot = sed_fphotons; A.offset = sed_offset;
+    A.sed_id = sed_id; A.redshift = redshift; A.mw_av = mw_av; A.mw_rv = mw_rv;
+    A.flux = flux; A.tables = tables + row_offset * (int64_t)n_pts;
+    A.band_hi = band_hi; A.n_obj = n_obj;
+    A.n_grid = n_grid; A.n_sed = n_sed; A.n_pts = n_pts; A.lds_stride = n_grid;
+    hipLaunchKernelGGL(k_object_spectra, dim3((unsigned)blocks), dim3(64 * SED_WAVES), (size_t)n_grid * SED_WAVES * sizeof(double),
+                       (hipStream_t)stream, A);
+    HIP_TRY(hipGetLastError());
+    return IMS_OK;
+}
+
+}  // extern "C"

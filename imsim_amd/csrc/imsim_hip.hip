@@ -8,9 +8,9 @@
 // pixel-boundary state and the image lines they touch.
 //
 // ONE translation unit, written as sections: ims_host.h (the library's host state and the helpers every entry point uses),
-// this file, then one file per subsystem that has been cut out of it (ims_readout.h .. ims_test.h).  A section holds its kernels,
-// its static host helpers and its own extern "C" block, and needs only what is included before it (DESIGN.md has the file map
-// and says what is still here).
+// this file, then one file per subsystem (ims_image.h .. ims_test.h, included at the end).  A section holds its kernels, its
+// static host helpers and its own extern "C" block, and needs only what is included before it (DESIGN.md has the file map).
+// This file is the hot path alone: the photon kernels, the joint rounds, the Silicon boundary state and their entry points.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -22,8 +22,6 @@
 #include <tuple>
 #include "ims_photon.h"
 #include "ims_fft.h"
-#include "ims_opd.h"
-#include "ims_sed.h"
 #include "ims_libs.h"           // hipFFT / RCCL looked up at run time (the handle types the host state names)
 
 using namespace ims;
@@ -39,6 +37,8 @@ __device__ __forceinline__ int64_t xcd_segment(int64_t b, int64_t n_segments)
     return (b % N_XCD) * per + (b / N_XCD);
 }
 
+// the last entry of an int64 prefix that is <= seg: the object of a segment here and in the PSF probes, the object of a grid
+// element on the FFT branch (ims_fft_branch.h), the object and the tile of a photon in ims_reshoot.h
 __device__ __forceinline__ int64_t find_object(const int64_t* __restrict__ prefix, int64_t n_objects, int64_t seg)
 {
     int64_t lo = 0, hi = n_objects;
@@ -2135,772 +2135,7 @@ __global__ __launch_bounds__(256) void k_refresh_list_j(const JointUpd* __restri
     }
 }
 
-// ---------------- LSST_Flat ----------------
-constexpr long long FLAT_ID_BASE = 0x7F00000000ll;      // object id space of the flat builder's Poisson streams
-
-// Silicon::fillWithPixelAreas: shoelace area of the (distorted) polygon of every pixel of one slot
-__global__ __launch_bounds__(256) void k_pixel_areas(const ims_sensor_t* __restrict__ sp, int slot, double* __restrict__ area,
-                                                     long long* __restrict__ sum_q32)
-{
-    const ims_sensor_t& s = *sp;
-    const ims_bf_slot_t bs = s.bf_slots[slot];
-    const SlotView sl = { bs.xmin, bs.ymin, bs.nx, bs.ny, bs.offset };
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= (int64_t)sl.nx * sl.ny) return;
-    const int i = (int)(p % sl.nx), j = (int)(p / sl.nx);
-    const int nv = 4 * s.num_vertices + 4;
-    double x0, y0, xp, yp, a2 = 0.0;
-    polygon_vertex(s, sl, i, j, 0, 1.0, x0, y0);
-    xp = x0; yp = y0;
-    for (int k = 1; k <= nv; ++k) {
-        double xk = x0, yk = y0;
-        if (k < nv) polygon_vertex(s, sl, i, j, k, 1.0, xk, yk);
-        a2 = a2 + (xp * yk - xk * yp);
-        xp = xk; yp = yk;
-    }
-    const double a = 0.5 * a2;
-    area[p] = a;
-    atomicAdd((unsigned long long*)sum_q32, (unsigned long long)(long long)floor(a * 0x1.0p32 + 0.5));
-}
-
-__global__ __launch_bounds__(256) void k_flat_add(const double* __restrict__ area, const double* __restrict__ base, double level,
-                                                  double inv_mean_area, uint64_t seed, int64_t iteration, int nx, int ny,
-                                                  double* __restrict__ image, double* __restrict__ delta)
-{
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= (int64_t)nx * ny) return;
-    double mean = level;
-    if (base != nullptr) mean = mean * base[p];
-    if (area != nullptr) mean = mean * (area[p] * inv_mean_area);
-    const double v = poisson(mean, seed, FLAT_ID_BASE + iteration, p);
-    image[p] = image[p] + v;
-    if (delta != nullptr) {
-        const int i = (int)(p % nx), j = (int)(p / nx);
-        delta[(int64_t)j * (nx + 1) + i] = delta[(int64_t)j * (nx + 1) + i] + v;
-    }
-}
-
 __global__ void k_clear_pristine(ims_sensor_t* sp) { sp->pristine_margin = -1.0; }
-
-__global__ __launch_bounds__(256) void k_zero_delta(const ims_sensor_t* __restrict__ sp, int64_t cell_begin, int64_t cell_count)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= cell_count) return;
-    sp->bf_delta[cell_begin + t] = 0.0;
-}
-
-__global__ __launch_bounds__(256) void k_image_add(double* __restrict__ dst, const double* __restrict__ src, int64_t n)
-{
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] += src[i];
-}
-
-__global__ __launch_bounds__(256) void k_image_to_float(const double* __restrict__ src, float* __restrict__ dst, int64_t n)
-{
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = (float)src[i];
-}
-
-// One workgroup per hit of a layer, a lane per span pixel.  The hits of a layer cover disjoint pixels (the caller's layering),
-// so the plain read-add-write below has no races, and each pixel sees its adds in layer order.  A footprint has some tens of
-// pixels: one wave per hit, the span of a pixel by binary search over the footprint's pixel prefix.
-__global__ __launch_bounds__(64) void k_paint_cosmic_rays(double* __restrict__ image, int32_t nx, int32_t ny,
-                                                          const ims_cr_span_t* __restrict__ spans, int64_t n_spans,
-                                                          const double* __restrict__ values, int64_t n_values,
-                                                          const ims_cr_hit_t* __restrict__ hits)
-{
-    const ims_cr_hit_t h = hits[blockIdx.x];
-    if (h.n_spans < 1 || h.first_span < 0 || (int64_t)h.first_span + h.n_spans > n_spans) return;
-    const int32_t base = spans[h.first_span].first_pixel;
-    for (int32_t k = threadIdx.x; k < h.n_pixels; k += blockDim.x) {
-        int32_t lo = h.first_span, hi = h.first_span + h.n_spans - 1;        // last span whose first pixel is <= k
-        while (lo < hi) {
-            const int32_t mid = lo + (hi - lo + 1) / 2;
-            if (spans[mid].first_pixel - base <= k) lo = mid;
-            else hi = mid - 1;
-        }
-        const ims_cr_span_t s = spans[lo];
-        const int32_t dx = k - (s.first_pixel - base);
-        if (dx < 0 || dx >= s.n || s.value_offset < 0 || s.value_offset + dx >= n_values) continue;
-        const int64_t row = (int64_t)h.y0 + s.row, col = (int64_t)h.x0 + s.col + dx;
-        if (row < 0 || row >= ny || col < 0 || col >= nx) continue;
-        image[row * nx + col] += values[s.value_offset + dx];
-    }
-}
-
-
-// ---------------- FFT branch ----------------
-__device__ __forceinline__ int64_t find_prefix(const int64_t* __restrict__ prefix, int64_t n, int64_t e)
-{
-    int64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (prefix[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// row and column of element `local` of a grid of row length `len` (FFT sizes are powers of two: a shift; half spectra -- len =
-// nfft / 2 + 1 -- and anything else: a 32-bit division, the grids hold fewer than 2^31 elements)
-__device__ __forceinline__ void row_col(int64_t local, int len, int& row, int& col)
-{
-    const uint32_t l = (uint32_t)local, n = (uint32_t)len;
-    if ((n & (n - 1u)) == 0u) { const int sh = 31 - __clz((int)n); row = (int)(l >> sh); col = (int)(l & (n - 1u)); }
-    else { row = (int)(l / n); col = (int)(l - (uint32_t)row * n); }
-}
-
-// The elementwise kernels of the FFT branch walk the back-to-back grids of their objects in SPANS: a workgroup owns `span` consecutive
-// elements (a multiple of 256, fft_span below), a wavefront 64 consecutive ones per pass.  The object of a wavefront's elements is
-// found ONCE per span (a bisection with scalar operands) and then only moved along when the wavefront's first element passes the
-// object's end; a wavefront that lies inside one object -- all of them but the few on a boundary -- calls the body with a UNIFORM object
-// number, so that the object's row and its prefix entry come by scalar loads.  (A grid-stride loop used to bisect in every pass: 13
-// dependent loads before the first useful one, `k_fft_finish` waited 67 % of its wave-cycles and moved 0.26 TB/s, round 6.)
-template <class Body>
-__device__ __forceinline__ void walk_span(const int64_t* __restrict__ prefix, int64_t n_objects, int64_t n_elems, int64_t span, Body&& body)
-{
-    const int64_t wg_begin = (int64_t)blockIdx.x * span;
-    int64_t wg_end = wg_begin + span;
-    if (wg_end > n_elems) wg_end = n_elems;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = (int)(threadIdx.x & 63u);
-    int64_t oi = -1, o_end = 0;
-    for (int64_t base = wg_begin + 64 * wave; base < wg_end; base += 256) {
-        if (oi < 0) { oi = find_prefix(prefix, n_objects, base); o_end = prefix[oi + 1]; }
-        else while (base >= o_end) { ++oi; o_end = prefix[oi + 1]; }
-        const int64_t el = base + lane;
-        if (base + 64 <= o_end) {
-            if (el < wg_end) body(el, oi);
-        } else if (el < wg_end) {
-            body(el, el < o_end ? oi : find_prefix(prefix, n_objects, el));
-        }
-    }
-}
-
-// 1 / (nfft * nfft) as ims_fft_inverse's scaling pass forms it on the host (powers of two: the exponent written directly)
-__device__ __forceinline__ double inv_n2(int nfft)
-{
-    const uint32_t n = (uint32_t)nfft;
-    if ((n & (n - 1u)) == 0u) return __longlong_as_double((long long)(1023 - 2 * (31 - __clz((int)n))) << 52);
-    return 1.0 / ((double)nfft * (double)nfft);
-}
-// a value of the real-space buffer as the image holds it (ims_fft_params_t.rbuf_raw)
-__device__ __forceinline__ double rbuf_value(const double* __restrict__ rbuf, int64_t at, bool raw, double scale)
-{
-    const double v = rbuf[at];
-    return raw ? v * scale : v;
-}
-
-// LDS tables of the pixel response for a workgroup whose span lies inside ONE object's half spectrum (every workgroup of a grid of
-// 1 024 or more): sinc along x for every column of the row, sinc along y (for ky and for -ky) for the few rows the span covers.
-constexpr int FILL_NH_MAX = 2049, FILL_ROWS_MAX = 264;      // grids up to 4096 (larger ones: no tables); 20 KB of LDS
-// The same workgroup on a box (IMS_PROF_BOX): qx / 2 = A j + B i' and qy / 2 = C j + D i' are affine in the grid indices, so their sines
-// come from {sin, cos} of (A j, C j) per column and of (B i', D i') per row by angle addition.  The columns are split in two levels,
-// j = 64 jh + jl (64 + 5 entries; one level and the rows would pass the 32 KB a workgroup may hold with five on a CU), the rows are
-// stored for +i' only (the mirrored row changes the sign of the sines).  10.7 KB more: 31.3 KB per workgroup.
-// Grids up to BOX_NFFT_MAX only.  The parts A jl, A 64 jh and B i' are rounded one by one, so where they cancel the sum misses the
-// h the plain form takes by some ulps of the PARTS, and sin / h by that over h: it grows with trail length x grid size (against the
-// numpy restatement of the tests, per unit flux: 2e-16 for 12" on 256, 3e-16 to 2e-15 for 30" on 512, 3e-14 to 6e-14 for 150" on 2048
-// and 8e-14 to 1e-13 for 400" on 4096 in a host emulation of this arithmetic behind Gaussians of sigma 0.4" to 0.3" -- the plain
-// form rounds h as numpy does and stays at 1.4e-15).
-// Neither is nearer to the exact spectrum, but larger grids keep the plain form and the bound the tests hold.
-constexpr int BOX_LO = 64, BOX_NFFT_MAX = 512, BOX_HI_MAX = (BOX_NFFT_MAX / 2 + 1 + BOX_LO - 1) / BOX_LO;
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_fft_kspace_fill(const ims_fft_params_t P, const ims_fft_object_t* __restrict__ objs,
-                                                         int64_t n_objects, const int64_t* __restrict__ prefix, int64_t n_elems, int64_t span,
-                                                         double* __restrict__ kbuf)
-{
-    __shared__ double sinc_x[FILL_NH_MAX];
-    __shared__ double sinc_y[2 * FILL_ROWS_MAX];
-    __shared__ double box_col[4 * (BOX_LO + BOX_HI_MAX)];
-    __shared__ double box_row[4 * FILL_ROWS_MAX];
-    // (uniform over the workgroup: formed from the block's number and scalar loads)
-    const int64_t wg_begin = (int64_t)blockIdx.x * span;
-    int64_t wg_end = wg_begin + span;
-    if (wg_end > n_elems) wg_end = n_elems;
-    bool tables = false, box_tables = false;
-    int row_first = 0;
-    if (P.n_alias <= 0 && wg_begin < wg_end) {
-        const int64_t o0 = find_prefix(prefix, n_objects, wg_begin);
-        const int64_t ob = prefix[o0];
-        if (wg_end <= prefix[o0 + 1]) {
-            const int n = objs[o0].nfft, nh = n / 2 + 1, half = n / 2;
-            row_first = (int)((wg_begin - ob) / nh);
-            const int row_last = (int)((wg_end - 1 - ob) / nh);
-            if (row_first > half) return;              // rows written by the threads of their mirror rows
-            if (nh <= FILL_NH_MAX && row_last - row_first + 1 <= FILL_ROWS_MAX) {
-                const double dk = TWO_PI / ((double)n * P.pixel_scale);
-                for (int j = threadIdx.x; j < nh; j += 256) sinc_x[j] = pixel_response((double)j * dk, P.pixel_scale);
-                for (int r = threadIdx.x; r < 2 * (row_last - row_first + 1); r += 256) {
-                    const double ky = (double)(row_first + (r >> 1)) * dk;
-                    sinc_y[r] = pixel_response((r & 1) ? -ky : ky, P.pixel_scale);
-                }
-                tables = true;
-                const ims_fft_object_t& ob0 = objs[o0];
-#ifndef IMS_FILL_BOX_PLAIN                 // (-DIMS_FILL_BOX_PLAIN: the box by box_response's dsincos everywhere, to measure against)
-                if (ob0.prof_ktable == IMS_PROF_BOX && n <= BOX_NFFT_MAX) {
-                    const int n_hi = (nh + BOX_LO - 1) / BOX_LO;
-                    for (int t = threadIdx.x; t < BOX_LO + n_hi; t += 256) {
-                        const double kx = (double)(t < BOX_LO ? t : BOX_LO * (t - BOX_LO)) * dk;
-                        dsincos(0.5 * (ob0.jac[0] * kx), box_col[4 * t], box_col[4 * t + 1]);
-                        dsincos(0.5 * (ob0.jac[1] * kx), box_col[4 * t + 2], box_col[4 * t + 3]);
-                    }
-                    for (int r = threadIdx.x; r < row_last - row_first + 1; r += 256) {
-                        const double ky = (double)(row_first + r) * dk;
-                        dsincos(0.5 * (ob0.jac[2] * ky), box_row[4 * r], box_row[4 * r + 1]);
-                        dsincos(0.5 * (ob0.jac[3] * ky), box_row[4 * r + 2], box_row[4 * r + 3]);
-                    }
-                    box_tables = true;
-                }
-#endif
-                __syncthreads();
-            }
-        }
-    }
-    walk_span(prefix, n_objects, n_elems, span, [&](int64_t el, int64_t oi) {
-        const ims_fft_object_t& o = objs[oi];
-        const int64_t local = el - prefix[oi];
-        const int nh = o.nfft / 2 + 1;
-        int i, j;
-        row_col(local, nh, i, j);
-        double re, im;
-        if (P.n_alias <= 0) {
-            // rows i and n - i share most of their arithmetic (kspace_pair): the thread of row 0 < i < n / 2 writes both, the
-            // threads of the rows beyond n / 2 have nothing to do (whole wavefronts of them: a row is nfft / 2 + 1 elements)
-            const int n = o.nfft, half = n / 2;
-            if (i > half) return;
-            if (i > 0 && i < half) {
-                const double dk = TWO_PI / ((double)n * P.pixel_scale);
-                double re2, im2;
-                if (box_tables) {
-                    const double tab[3] = { sinc_x[j], sinc_y[2 * (i - row_first)], sinc_y[2 * (i - row_first) + 1] };
-                    const double* lo = box_col + 4 * (j & (BOX_LO - 1));
-                    const double* hi = box_col + 4 * (BOX_LO + j / BOX_LO);
-                    const double* rw = box_row + 4 * (i - row_first);
-                    const double box[8] = { fma(lo[0], hi[1], lo[1] * hi[0]), fma(lo[1], hi[1], -(lo[0] * hi[0])),
-                                            fma(lo[2], hi[3], lo[3] * hi[2]), fma(lo[3], hi[3], -(lo[2] * hi[2])),
-                                            rw[0], rw[1], rw[2], rw[3] };
-                    kspace_pair(P, o, (double)j * dk, (double)i * dk, re, im, re2, im2, tab, box);
-                } else if (tables) {
-                    const double tab[3] = { sinc_x[j], sinc_y[2 * (i - row_first)], sinc_y[2 * (i - row_first) + 1] };
-                    kspace_pair(P, o, (double)j * dk, (double)i * dk, re, im, re2, im2, tab);
-                } else {
-                    kspace_pair(P, o, (double)j * dk, (double)i * dk, re, im, re2, im2);
-                }
-                const int64_t at2 = o.k_offset + (int64_t)(n - i) * nh + j;
-                kbuf[2 * (o.k_offset + local)] = re;
-                kbuf[2 * (o.k_offset + local) + 1] = im;
-                kbuf[2 * at2] = re2;
-                kbuf[2 * at2 + 1] = im2;
-                return;
-            }
-        }
-        kspace_value(P, o, i, j, re, im);
-        kbuf[2 * (o.k_offset + local)] = re;
-        kbuf[2 * (o.k_offset + local) + 1] = im;
-    });
-}
-
-// saturated bounding box of every object (saturated_region, imsim/diffraction_fft.py:211-227)
-__global__ __launch_bounds__(256) void k_fft_bbox(const ims_fft_params_t P, const ims_fft_object_t* __restrict__ objs,
-                                                  int64_t n_objects, const int64_t* __restrict__ prefix, int64_t n_pix, int64_t span,
-                                                  const double* __restrict__ rbuf, int32_t* __restrict__ bbox)
-{
-    walk_span(prefix, n_objects, n_pix, span, [&](int64_t el, int64_t oi) {
-        const ims_fft_object_t& o = objs[oi];
-        const int64_t local = el - prefix[oi];
-        int iy, ix;
-        row_col(local, o.nfft, iy, ix);
-        const int px = o.x0 + ix, py = o.y0 + iy;
-        if (px < o.stamp_xmin || px > o.stamp_xmax || py < o.stamp_ymin || py > o.stamp_ymax) return;
-        if (rbuf_value(rbuf, o.r_offset + local, P.rbuf_raw != 0, inv_n2(o.nfft)) > P.spikes.threshold) {
-            atomicMin(&bbox[4 * oi + 0], iy); atomicMax(&bbox[4 * oi + 1], iy);
-            atomicMin(&bbox[4 * oi + 2], ix); atomicMax(&bbox[4 * oi + 3], ix);
-        }
-    });
-}
-
-// ims_spikes_t.tab_*: one thread per row a of the stencil; b from +cutoff down to -cutoff.  row_ptr == NULL: count only.
-__global__ __launch_bounds__(64) void k_fft_spike_table(const ims_spikes_t k, const int32_t* __restrict__ row_ptr, int32_t* __restrict__ row_count,
-                                                        int32_t* __restrict__ col, double* __restrict__ val)
-{
-    const int row = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (row > 2 * k.cutoff) return;
-    const int a = row - k.cutoff;
-    int n = 0;
-    const int base = row_ptr ? row_ptr[row] : 0;
-    for (int b = k.cutoff; b >= -k.cutoff; --b) {
-        const double sv = spike_stencil(k, a, b);
-        if (sv == 0.0) continue;
-        if (row_ptr) { col[base + n] = b; val[base + n] = sv / k.norm; }
-        ++n;
-    }
-    if (!row_ptr) row_count[row] = n;
-}
-
-// convolve_region (imsim/diffraction_fft.py:170-208): clipped image with the box zeroed + box (x) stencil
-// Far from the arms of EVERY source pixel's cross the whole spike sum of a pixel is exact zeros: the offsets from the pixel to the
-// sources differ from the offset to the box centre by at most half the box, so if even the nearer arm of the centre's cross is
-// further away than that (plus the stencil's own margins, ims_fft.h spike_stencil), no term can be non-zero.  97 % of a 4096^2 stamp.
-__device__ __forceinline__ bool spike_sum_is_zero(const ims_spikes_t& k, int iy, int ix, int r0, int r1, int c0, int c1)
-{
-    const double ac = (double)iy - 0.5 * (double)(r0 + r1), bc = (double)ix - 0.5 * (double)(c0 + c1);
-    const double ha = 0.5 * (double)(r1 - r0), hb = 0.5 * (double)(c1 - c0);
-    const double e = fabs(k.cos0) * ha + fabs(k.sin0) * hb + fabs(k.sin0) * ha + fabs(k.cos0) * hb;
-    const double xc = k.cos0 * ac + k.sin0 * bc, yc = -k.sin0 * ac + k.cos0 * bc;
-    const double mc = (fabs(xc) < fabs(yc) ? fabs(xc) : fabs(yc)) - e;
-    const double rmax = sqrt(ac * ac + bc * bc) + sqrt(ha * ha + hb * hb) + 1.0;
-    const double lim = 0.5 * fabs(k.d_alpha) + 1.0e-6;
-    return mc > 1.0 + 1.0e-3 && mc - 1.0e-3 > lim * rmax;
-}
-
-// the spike sum of pixel (iy, ix) of object o over the saturated box rows r0 .. r1, columns c0 .. c1 (DiffractionFFT.apply's convolution)
-__device__ __forceinline__ double spike_sum(const ims_fft_params_t& P, const ims_fft_object_t& o, int iy, int ix, int r0, int r1, int c0,
-                                            int c1, const double* __restrict__ rin, bool raw, double scale)
-{
-    double acc = 0.0;
-    if (P.spikes.tab_row != nullptr) {
-        // The stencil's non-zero entries come out of the visit's table (ims_spikes_t.tab_*): of source row ry the entries of
-        // stencil row a = iy - ry whose column offset b puts the source column ix - b inside the box, in ascending source
-        // column -- the terms the loops below find among their candidates, in the same order, each formed by the same
-        // operations (stencil / norm in the table's kernel, times the source here), without the three arctangents per term
-        // and the ~16 candidates per row: the same sum.  (A star's spike stencil was 1.1 ms of a CCD's front, round 6.)
-        // The walk is a chain of dependent loads (row pointer -> column offsets -> source pixels) on a few lanes of a wavefront, so
-        // the loads are asked for in batches: the NEXT row's pointer while this row is worked on (rows are consecutive in the
-        // table: row a - 1 ends where row a begins), four entries' offsets and values at once, then their four source pixels, then
-        // the four terms in the table's order -- the entries with blo <= b <= bhi, a contiguous run of the descending columns, as before.
-        const ims_spikes_t& k = P.spikes;
-        const int blo = ix - c1, bhi = ix - c0;
-        const int ry_lo = r0 > iy - k.cutoff ? r0 : iy - k.cutoff, ry_hi = r1 < iy + k.cutoff ? r1 : iy + k.cutoff;
-        if (ry_lo <= ry_hi) {
-            int a = iy - ry_lo;
-            int e0 = k.tab_row[a + k.cutoff], e1 = k.tab_row[a + k.cutoff + 1];
-            for (int ry = ry_lo; ry <= ry_hi; ++ry, --a) {
-                const int e_next = ry < ry_hi ? k.tab_row[a - 1 + k.cutoff] : 0;
-                int e = e0;
-                if (e1 - e > 16) {                         // an arm along this row: the first entry with b <= bhi by bisection
-                    int lo = e, hi = e1;
-                    while (lo < hi) { const int mid = (lo + hi) >> 1; if (k.tab_col[mid] > bhi) lo = mid + 1; else hi = mid; }
-                    e = lo;
-                }
-                const int64_t row_at = o.r_offset + (int64_t)ry * o.nfft + ix;
-                for (; e < e1; e += 4) {
-                    int b[4];
-                    double tv[4], sv[4];
-                    bool use[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int eq = e + q < e1 ? e + q : e1 - 1;
-                        b[q] = k.tab_col[eq]; tv[q] = k.tab_val[eq];
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        use[q] = e + q < e1 && b[q] <= bhi && b[q] >= blo;
-                        sv[q] = rbuf_value(rin, row_at - (use[q] ? b[q] : bhi), raw, scale);      // (not used: the box's first column)
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (use[q]) { const double src = sv[q] < 0.0 ? 0.0 : sv[q]; acc = acc + tv[q] * src; }
-                    if (b[3] < blo || b[0] < blo) break;       // descending columns: nothing further down is inside the box
-                }
-                e1 = e0; e0 = e_next;
-            }
-        }
-    } else {
-        // Of a source row only the columns near the two arms through this pixel can contribute (|xr| or |yr| within the
-        // stencil's reach T: one interval of columns each, ims_fft.h spike_stencil); everything else in the row is an exact
-        // zero.  The columns are visited in ascending order as before, so the sum is the same sum -- a saturated star's
-        // box is 100 x 100 source pixels, of which a target pixel on an arm needs ~16 per row.
-        const ims_spikes_t& k = P.spikes;
-        const double lim = 0.5 * fabs(k.d_alpha) + 1.0e-6;
-        const double bfar = fabs((double)(ix - c0)) > fabs((double)(ix - c1)) ? fabs((double)(ix - c0)) : fabs((double)(ix - c1));
-        const bool has_s = fabs(k.sin0) > 1.0e-12, has_c = fabs(k.cos0) > 1.0e-12;
-        const double inv_s = has_s ? 1.0 / k.sin0 : 0.0, inv_c = has_c ? 1.0 / k.cos0 : 0.0;
-        for (int ry = r0; ry <= r1; ++ry) {
-            const int a = iy - ry;
-            if (a < -k.cutoff || a > k.cutoff) continue;
-            const double da = (double)a;
-            const double T = 1.0 + 1.0e-3 + lim * sqrt(da * da + bfar * bfar);
-            int lo[2], hi[2];
-            // |cos0 a + sin0 b| <= T
-            if (has_s) {
-                const double b1 = (-T - k.cos0 * da) * inv_s, b2 = (T - k.cos0 * da) * inv_s;
-                const double bl = b1 < b2 ? b1 : b2, bh = b1 < b2 ? b2 : b1;
-                lo[0] = (int)floor((double)ix - bh) - 1; hi[0] = (int)ceil((double)ix - bl) + 1;
-            } else if (fabs(k.cos0 * da) <= T) { lo[0] = c0; hi[0] = c1; }
-            else { lo[0] = 1; hi[0] = 0; }
-            // |-sin0 a + cos0 b| <= T
-            if (has_c) {
-                const double b1 = (-T + k.sin0 * da) * inv_c, b2 = (T + k.sin0 * da) * inv_c;
-                const double bl = b1 < b2 ? b1 : b2, bh = b1 < b2 ? b2 : b1;
-                lo[1] = (int)floor((double)ix - bh) - 1; hi[1] = (int)ceil((double)ix - bl) + 1;
-            } else if (fabs(k.sin0 * da) <= T) { lo[1] = c0; hi[1] = c1; }
-            else { lo[1] = 1; hi[1] = 0; }
-            for (int q = 0; q < 2; ++q) { if (lo[q] < c0) lo[q] = c0; if (hi[q] > c1) hi[q] = c1; }
-            if (lo[1] < lo[0]) { const int tl = lo[0], th = hi[0]; lo[0] = lo[1]; hi[0] = hi[1]; lo[1] = tl; hi[1] = th; }
-            if (hi[0] >= lo[0] && hi[1] >= lo[1] && lo[1] <= hi[0] + 1) { if (hi[1] > hi[0]) hi[0] = hi[1]; lo[1] = 1; hi[1] = 0; }   // one run
-            for (int q = 0; q < 2; ++q)
-                for (int rx = lo[q]; rx <= hi[q]; ++rx) {
-                    const int b = ix - rx;
-                    if (b < -k.cutoff || b > k.cutoff) continue;
-                    double src = rbuf_value(rin, o.r_offset + (int64_t)ry * o.nfft + rx, raw, scale);
-                    if (src < 0.0) src = 0.0;
-                    acc = acc + spike_stencil(k, a, b) / k.norm * src;
-                }
-        }
-    }
-    return acc;
-}
-
-__global__ __launch_bounds__(256) void k_fft_spikes(const ims_fft_params_t P, const ims_fft_object_t* __restrict__ objs,
-                                                    int64_t n_objects, const int64_t* __restrict__ prefix, int64_t n_pix, int64_t span,
-                                                    const double* __restrict__ rin, double* __restrict__ rout,
-                                                    const int32_t* __restrict__ bbox, const unsigned int* __restrict__ only_if_over,
-                                                    unsigned int over_cap)
-{
-    // (the fallback of the listed form below: runs only when the list ran over)
-    if (only_if_over != nullptr && only_if_over[0] <= over_cap) return;
-    walk_span(prefix, n_objects, n_pix, span, [&](int64_t el, int64_t oi) {
-        const ims_fft_object_t& o = objs[oi];
-        const int64_t local = el - prefix[oi];
-        int iy, ix;
-        row_col(local, o.nfft, iy, ix);
-        const bool raw = P.rbuf_raw != 0;
-        const double scale = inv_n2(o.nfft);
-        double v = rbuf_value(rin, o.r_offset + local, raw, scale);
-        if (v < 0.0) v = 0.0;
-        const int px = o.x0 + ix, py = o.y0 + iy;
-        const bool in_stamp = !(px < o.stamp_xmin || px > o.stamp_xmax || py < o.stamp_ymin || py > o.stamp_ymax);
-        const int r0 = bbox[4 * oi + 0], r1 = bbox[4 * oi + 1], c0 = bbox[4 * oi + 2], c1 = bbox[4 * oi + 3];
-        if (P.spikes.enabled && in_stamp && r1 >= r0) {
-            if (iy >= r0 && iy <= r1 && ix >= c0 && ix <= c1) v = 0.0;
-            double acc = 0.0;
-            if (!spike_sum_is_zero(P.spikes, iy, ix, r0, r1, c0, c1)) acc = spike_sum(P, o, iy, ix, r0, r1, c0, c1, rin, raw, scale);
-            v = v + acc;
-        }
-        rout[o.r_offset + local] = v;
-    });
-}
-
-// The spike step in two launches (ims_fft_spikes_listed).  This one streams: clip, the saturated box to zero, the image written --
-// and the pixels whose spike sum is NOT known to be zero (3 % of a bright star's stamp: the arms) appended to a list, object << 40 |
-// element of the object.  Light (no table walk in it: 40 registers instead of 98), so that its 16 bytes per pixel move at the
-// rate of a copy; the arms' sums are then formed by k_fft_spikes_arms with every lane at work, not three in a wavefront.
-__global__ __launch_bounds__(256) void k_fft_spikes_stream(const ims_fft_params_t P, const ims_fft_object_t* __restrict__ objs,
-                                                           int64_t n_objects, const int64_t* __restrict__ prefix, int64_t n_pix, int64_t span,
-                                                           const double* __restrict__ rin, double* __restrict__ rout,
-                                                           const int32_t* __restrict__ bbox, unsigned long long* __restrict__ list,
-                                                           unsigned int cap, unsigned int* __restrict__ count)
-{
-    walk_span(prefix, n_objects, n_pix, span, [&](int64_t el, int64_t oi) {
-        const ims_fft_object_t& o = objs[oi];
-        const int64_t local = el - prefix[oi];
-        int iy, ix;
-        row_col(local, o.nfft, iy, ix);
-        double v = rbuf_value(rin, o.r_offset + local, P.rbuf_raw != 0, inv_n2(o.nfft));
-        if (v < 0.0) v = 0.0;
-        const int px = o.x0 + ix, py = o.y0 + iy;
-        const bool in_stamp = !(px < o.stamp_xmin || px > o.stamp_xmax || py < o.stamp_ymin || py > o.stamp_ymax);
-        const int r0 = bbox[4 * oi + 0], r1 = bbox[4 * oi + 1], c0 = bbox[4 * oi + 2], c1 = bbox[4 * oi + 3];
-        bool want = false;
-        if (P.spikes.enabled && in_stamp && r1 >= r0) {
-            if (iy >= r0 && iy <= r1 && ix >= c0 && ix <= c1) v = 0.0;
-            want = !spike_sum_is_zero(P.spikes, iy, ix, r0, r1, c0, c1);
-        }
-        rout[o.r_offset + local] = v;
-        // one addition to the counter per wavefront
-        const unsigned long long m = __ballot(want);
-        if (m != 0ull) {
-            const int lane = (int)(threadIdx.x & 63u), lead = __ffsll((long long)m) - 1;
-            unsigned int base = 0u;
-            if (lane == lead) base = atomicAdd(count, (unsigned int)__popcll(m));
-            base = __shfl(base, lead, 64);
-            const unsigned int at = base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
-            if (want && at < cap) list[at] = ((unsigned long long)oi << 40) | (unsigned long long)local;
-        }
-    });
-}
-
-__global__ __launch_bounds__(256) void k_fft_spikes_arms(const ims_fft_params_t P, const ims_fft_object_t* __restrict__ objs,
-                                                         const double* __restrict__ rin, double* __restrict__ rout,
-                                                         const int32_t* __restrict__ bbox, const unsigned long long* __restrict__ list,
-                                                         unsigned int cap, const unsigned int* __restrict__ count)
-{
-    const unsigned int n = count[0];
-    if (n > cap) return;                          // the list ran over: k_fft_spikes does the whole step again
-    const unsigned int stride = gridDim.x * blockDim.x;
-    for (unsigned int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) {
-        const unsigned long long e = list[t];
-        const int64_t oi = (int64_t)(e >> 40), local = (int64_t)(e & ((1ull << 40) - 1ull));
-        const ims_fft_object_t& o = objs[oi];
-        int iy, ix;
-        row_col(local, o.nfft, iy, ix);
-        const int r0 = bbox[4 * oi + 0], r1 = bbox[4 * oi + 1], c0 = bbox[4 * oi + 2], c1 = bbox[4 * oi + 3];
-        const double acc = spike_sum(P, o, iy, ix, r0, r1, c0, c1, rin, P.rbuf_raw != 0, inv_n2(o.nfft));
-        rout[o.r_offset + local] = rout[o.r_offset + local] + acc;
-    }
-}
-
-// clip, Poisson noise, stamp -> CCD add (stamp.py:519-524); realized flux = noise-free sum inside the stamp
-__global__ __launch_bounds__(256) void k_fft_finish(const ims_fft_params_t P, const ims_fft_object_t* __restrict__ objs,
-                                                    int64_t n_objects, const int64_t* __restrict__ prefix, int64_t n_pix, int64_t span,
-                                                    const double* __restrict__ rbuf)
-{
-    walk_span(prefix, n_objects, n_pix, span, [&](int64_t el, int64_t oi) {
-        const ims_fft_object_t& o = objs[oi];
-        const int64_t local = el - prefix[oi];
-        int iy, ix;
-        row_col(local, o.nfft, iy, ix);
-        const int px = o.x0 + ix, py = o.y0 + iy;
-        if (px < o.stamp_xmin || px > o.stamp_xmax || py < o.stamp_ymin || py > o.stamp_ymax) return;
-        double v = rbuf_value(rbuf, o.r_offset + local, P.rbuf_raw != 0, inv_n2(o.nfft));
-        if (v < 0.0) v = 0.0;
-        if (P.realized_flux != nullptr && v != 0.0) unsafeAtomicAdd(P.realized_flux + oi, v);
-        if (P.add_noise) v = poisson(v, P.seed, o.obj_id, local);
-        const int cxp = px - P.xmin, cyp = py - P.ymin;
-        if (cxp < 0 || cxp >= P.nx || cyp < 0 || cyp >= P.ny || v == 0.0) return;
-        unsafeAtomicAdd(P.image + ((int64_t)cyp * P.nx + cxp), v);
-    });
-}
-
-// ---------------- object table on the device (include/imsim_hip.h: ims_build_object_table) ----------------
-// One thread per catalog source.  The test-side CPU restatement repeats this arithmetic; the formulas are those of
-// imsim_amd/catalog.py (the numpy builder, which stays the portable host path).
-__device__ __forceinline__ int good_image_size(double stepk, double pixel_scale)
-{
-    // GSObject.getGoodImageSize: N = ceil(2 pi / (stepk * scale)) rounded up to even
-    const double nn = ceil(ddiv(TWO_PI, stepk * pixel_scale));
-    const long long n = (long long)nn;
-    return (int)(2 * ((n + 1) / 2));
-}
-
-// get_good_phot_stamp_size1 (imsim/stamp_utils.py:293-354) for a transformed Sersic profile: grow the square of N pixels by 10 %
-// until xValue on its four edge midpoints and four corners is below `keep`, cap at nmax, shrink while the next smaller square
-// still is (not below 64).  j0 .. j3: the profile's affine (sky = J profile); amp = flux I(0) / |det J|.
-__device__ __forceinline__ double sersic_edge_max(double h, double j0, double j1, double j2, double j3, double det, double hlr,
-                                                  double amp, double b, double inv_n)
-{
-    // the eight points: (h, 0) (-h, 0) (0, h) (0, -h) (h, h) (h, -h) (-h, h) (-h, -h); the profile is point-symmetric, so four suffice
-    const double px[4] = { h, 0.0, h, h }, py[4] = { 0.0, h, h, -h };
-    double best = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double u = ddiv(j3 * px[k] - j1 * py[k], det), v = ddiv(-j2 * px[k] + j0 * py[k], det);
-        const double r = ddiv(dsqrt0(u * u + v * v), hlr);
-        const double val = amp * dexp(-b * dpow(r, inv_n));
-        best = val > best ? val : best;
-    }
-    return best;
-}
-
-__device__ __forceinline__ long long phot_stamp_size1(int own, double keep, int nmax, double pixel_scale, double j0, double j1, double j2,
-                                                      double j3, double hlr, double flux, double norm, double b, double inv_n)
-{
-    const double det = j0 * j3 - j1 * j2;
-    const double amp = ddiv(flux * norm, hlr * hlr * fabs(det));
-    double N = (double)own;
-    bool active = N < (double)nmax;
-    for (int it = 0; it < 200 && active; ++it) {
-        const double mv = sersic_edge_max(N * 0.5 * pixel_scale, j0, j1, j2, j3, det, hlr, amp, b, inv_n);
-        if (mv < keep) break;
-        N = N * 1.1;
-        active = N < (double)nmax;
-    }
-    if (N > (double)nmax) N = (double)nmax;
-    active = N >= 64.0 * 1.1;
-    for (int it = 0; it < 200 && active; ++it) {
-        const double mv = sersic_edge_max(ddiv(N, 2.0 * 1.1) * pixel_scale, j0, j1, j2, j3, det, hlr, amp, b, inv_n);
-        if (mv > keep) break;
-        N = ddiv(N, 1.1);
-        active = N >= 64.0 * 1.1;
-    }
-    return (long long)N;
-}
-
-__global__ __launch_bounds__(256) void k_build_object_table(const ims_catalog_t C, const ims_optics_t* __restrict__ optics,
-                                                            ims_object_t* __restrict__ rows, ims_object_meta_t* __restrict__ meta)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= C.n) return;
-    ims_object_t o;
-    memset(&o, 0, sizeof(o));
-    ims_object_meta_t m = { 0, 0, 0 };
-    const int kind = C.kind[i];
-    const double nominal = C.nominal_flux[i];
-    const int64_t id = C.obj_id ? C.obj_id[i] : i;
-    const int64_t phot = C.phot_flux ? C.phot_flux[i] : (int64_t)poisson(nominal, C.seed, id, (int64_t)IMS_FLUX_PIXEL);
-    if (kind < 0 || kind > 2) {                       // knots, streaks, FITS stamps: the host writes these rows -- with the photon
-        m.flags = IMS_META_HOST_ROW;                  // count realised HERE, by the rule of every other object (same stream, same seed)
-        m.n_phot = phot;
-        rows[i] = o; meta[i] = m;
-        return;
-    }
-    const double x = C.x[i], y = C.y[i];
-    o.obj_id = id; o.phot_first = 0; o.n_phot = phot;
-    o.x0 = x; o.y0 = y; o.flux_per_photon = 1.0;
-    // profile and its affine
-    double j0 = 1.0, j1 = 0.0, j2 = 0.0, j3 = 1.0;
-    if (kind == 0) {
-        o.prof_table = IMS_PROF_POINT; o.prof_scale = 0.0;
-    } else {
-        o.prof_table = C.prof_table[i]; o.prof_scale = C.hlr[i];
-        const double q = C.q[i];
-        const double g = ddiv(1.0 - q, 1.0 + q);
-        double s2, c2;
-        dsincos(2.0 * ((90.0 - C.pa[i]) * 0.017453292519943295), s2, c2);         // beta = 90 deg - pa (flip_g2, instcat.py:503-508)
-        const double f = ddiv(1.0, dsqrt0(1.0 - g * g));
-        const double sg1 = g * c2, sg2 = g * s2;
-        j0 = f * (1.0 + sg1); j1 = f * sg2; j2 = f * sg2; j3 = f * (1.0 - sg1);
-        if (C.g1 != nullptr) {
-            const double l1 = C.g1[i], l2 = C.g2[i];
-            const double lg2 = l1 * l1 + l2 * l2;
-            const double lf = ddiv(dsqrt0(C.mu[i]), dsqrt0(1.0 - lg2));
-            const double a0 = lf * (1.0 + l1), a1 = lf * l2, a2 = lf * l2, a3 = lf * (1.0 - l1);
-            const double b0 = j0, b1 = j1, b2 = j2, b3 = j3;
-            j0 = a0 * b0 + a1 * b2; j1 = a0 * b1 + a1 * b3; j2 = a2 * b0 + a3 * b2; j3 = a2 * b1 + a3 * b3;
-        }
-    }
-    o.jac[0] = j0; o.jac[1] = j1; o.jac[2] = j2; o.jac[3] = j3;
-    // local WCS: analytic jacobian of pixel -> (u west, v north) [arcsec] at image_pos, inverted
-    const ims_tansip_t& w = optics->img_wcs;
-    double p[3];
-    {
-        double u = x - w.crpix[0], v = y - w.crpix[1];
-        double fu = 0.0, fv = 0.0, gu = 0.0, gv = 0.0;
-        if (w.order > 0) {
-            double f, g;
-            sip_value_grad(w.a, u, v, f, fu, fv);
-            sip_value_grad(w.b, u, v, g, gu, gv);
-            u = u + f; v = v + g;
-        }
-        const double Ux = 1.0 + fu, Uy = fv, Vx = gu, Vy = 1.0 + gv;
-        const double xi = w.cd[0] * u + w.cd[1] * v, eta = w.cd[2] * u + w.cd[3] * v;
-        const double xi_x = w.cd[0] * Ux + w.cd[1] * Vx, xi_y = w.cd[0] * Uy + w.cd[1] * Vy;
-        const double et_x = w.cd[2] * Ux + w.cd[3] * Vx, et_y = w.cd[2] * Uy + w.cd[3] * Vy;
-        double px[3], py[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            p[k] = w.rot[k] + w.rot[3 + k] * xi + w.rot[6 + k] * eta;
-            px[k] = w.rot[3 + k] * xi_x + w.rot[6 + k] * et_x;
-            py[k] = w.rot[3 + k] * xi_y + w.rot[6 + k] * et_y;
-        }
-        const double inv = ddiv(1.0, dsqrt0(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]));
-        p[0] = p[0] * inv; p[1] = p[1] * inv; p[2] = p[2] * inv;                   // unit vector of the object
-        const double cd = dsqrt0(p[0] * p[0] + p[1] * p[1]), icd = ddiv(1.0, cd);
-        const double e0 = -p[1] * icd, e1 = p[0] * icd;                             // east = pole x p, normalised
-        const double n0 = -p[2] * e1, n1 = p[2] * e0, n2 = p[0] * e1 - p[1] * e0;   // north = p x east
-        const double k = 206264.80624709636 * inv;                                  // arcsec per radian over |P|
-        const double dudx = -(px[0] * e0 + px[1] * e1) * k, dudy = -(py[0] * e0 + py[1] * e1) * k;
-        const double dvdx = (px[0] * n0 + px[1] * n1 + px[2] * n2) * k, dvdy = (py[0] * n0 + py[1] * n1 + py[2] * n2) * k;
-        const double idet = ddiv(1.0, dudx * dvdy - dudy * dvdx);
-        o.winv[0] = dvdy * idet; o.winv[1] = -dudy * idet; o.winv[2] = -dvdx * idet; o.winv[3] = dudx * idet;
-        // PhotonDCR: zenith distance and parallactic angle of this object, from the zenith's components along east / north
-        const double cz = p[0] * C.zenith[0] + p[1] * C.zenith[1] + p[2] * C.zenith[2];
-        const double ez = e0 * C.zenith[0] + e1 * C.zenith[1];
-        const double nz = n0 * C.zenith[0] + n1 * C.zenith[1] + n2 * C.zenith[2];
-        const double hz = dsqrt0(ez * ez + nz * nz);
-        o.dcr_tanz = ddiv(hz, cz);
-        o.dcr_sinp = hz > 0.0 ? ddiv(ez, hz) : 0.0;
-        o.dcr_cosp = hz > 0.0 ? ddiv(nz, hz) : 1.0;
-        if (C.has_field) {
-            double thx, thy;
-            wcs_vec_to_pix(optics->icrf_to_field, p, thx, thy);
-            o.atm_tan_x = thx; o.atm_tan_y = thy;
-        }
-    }
-    o.sed_table = C.sed_table ? C.sed_table[i] : C.sed_table_all;
-    o.sed_wave = 0.0;
-    o.flags = nominal < C.max_flux_simple ? IMS_OBJ_FAINT : 0;
-    o.bf_state = 0;
-    // stamp size (stamp.py:205-232)
-    int size = C.stamp_size ? C.stamp_size[i] : 0;
-    if (size <= 0) {
-        if (nominal < C.tiny_flux) size = 32;
-        else if (kind == 0) {
-            const double ft = ddiv(C.noise_var, nominal);
-            int k = 0;                                                   // index 0: the default folding threshold
-            if (ft < 5.0e-3 && ft != 0.0) k = (int)(-floor(dlog(ft)));
-            if (k >= C.n_star_size) k = C.n_star_size - 1;
-            size = C.star_size[k];
-        } else {
-            const double s1 = j0 * j0 + j1 * j1 + j2 * j2 + j3 * j3;
-            const double dd = j0 * j0 + j1 * j1 - j2 * j2 - j3 * j3, od = j0 * j2 + j1 * j3;
-            const double s2 = dsqrt0(fmax(dd * dd + 4.0 * od * od, 0.0));
-            const double smax = dsqrt0(0.5 * (s1 + s2));
-            int t = o.prof_table;
-            if (t < 0) t = 0;
-            if (t >= C.n_gal_radius) t = C.n_gal_radius - 1;
-            const double rr = C.gal_radius[t] * C.hlr[i] * smax;
-            constexpr double PI_ = 3.14159265358979323846;
-            const double stepk = ddiv(1.0, dsqrt0(ddiv(rr * rr, PI_ * PI_) + ddiv(1.0, C.dg_stepk * C.dg_stepk)));
-            size = good_image_size(stepk, C.pixel_scale);
-            if (nominal > 10.0 * (double)size * (double)size || size > C.nmax) {
-                if (C.sb_tables) {
-                    // bright or oversized: the size follows from the surface brightness at the stamp's edge (stamp_utils.py:196-220)
-                    const int own = good_image_size(ddiv(PI_, rr), C.pixel_scale);
-                    const double flux = C.sb_flux ? C.sb_flux[i] : nominal;
-                    const double hl = C.hlr[i];
-                    const long long g1 = phot_stamp_size1(own, C.keep_sb, C.nmax, C.pixel_scale, j0, j1, j2, j3, hl, flux, C.sersic_norm[t],
-                                                          C.sersic_b[t], C.sersic_inv_n[t]);
-                    long long sz = (long long)dsqrt0((double)g1 * (double)g1 + (double)C.psf_size_keep * (double)C.psf_size_keep);
-                    if (sz > C.nmax) {
-                        const long long g3 = phot_stamp_size1(own, 3.0 * C.keep_sb, C.nmax, C.pixel_scale, j0, j1, j2, j3, hl, flux,
-                                                              C.sersic_norm[t], C.sersic_b[t], C.sersic_inv_n[t]);
-                        sz = (long long)dsqrt0((double)g3 * (double)g3 + (double)C.psf_size_keep3 * (double)C.psf_size_keep3);
-                    }
-                    size = (int)(sz > C.nmax ? C.nmax : sz);
-                } else {
-                    m.flags |= IMS_META_SIZE_PENDING;
-                }
-            }
-            if (size > C.nmax) size = C.nmax;
-        }
-    }
-    const long long icx = (long long)floor(x + 0.5), icy = (long long)floor(y + 0.5);
-    o.stamp_xmin = (int)(icx - size / 2); o.stamp_xmax = (int)(icx - size / 2 + size - 1);
-    o.stamp_ymin = (int)(icy - size / 2); o.stamp_ymax = (int)(icy - size / 2 + size - 1);
-    m.n_phot = phot; m.size = size;
-    rows[i] = o; meta[i] = m;
-}
-
-__global__ __launch_bounds__(256) void k_patch_stamp_sizes(ims_object_t* __restrict__ rows, ims_object_meta_t* __restrict__ meta,
-                                                           const int64_t* __restrict__ index, const int32_t* __restrict__ size, int64_t n)
-{
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
-    ims_object_t& o = rows[index[k]];
-    const int sz = size[k];
-    const long long icx = (long long)floor(o.x0 + 0.5), icy = (long long)floor(o.y0 + 0.5);
-    o.stamp_xmin = (int)(icx - sz / 2); o.stamp_xmax = (int)(icx - sz / 2 + sz - 1);
-    o.stamp_ymin = (int)(icy - sz / 2); o.stamp_ymax = (int)(icy - sz / 2 + sz - 1);
-    meta[index[k]].size = sz;
-    meta[index[k]].flags &= ~IMS_META_SIZE_PENDING;
-}
-
-// dst[k] = rows[index[k]] with the launch's photon range and boundary slot: 256-byte rows move as 16 uint4 per row, one row per
-// 16 lanes
-__global__ __launch_bounds__(256) void k_gather_rows(const ims_object_t* __restrict__ rows, const int64_t* __restrict__ index,
-                                                     const int64_t* __restrict__ first, const int64_t* __restrict__ count,
-                                                     const int32_t* __restrict__ bf_state, int clear_flags,
-                                                     ims_object_t* __restrict__ dst, int64_t n)
-{
-    static_assert(sizeof(ims_object_t) == 256, "row size");
-    static_assert(offsetof(ims_object_t, phot_first) == 8 && offsetof(ims_object_t, n_phot) == 16 &&
-                  offsetof(ims_object_t, bf_state) == 172 && offsetof(ims_object_t, flags) == 152, "row layout");
-    const int64_t k = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
-    const int part = threadIdx.x & 15;
-    if (k >= n) return;
-    uint4 v = ((const uint4*)(rows + index[k]))[part];
-    if (part == 0 && first != nullptr) {                       // bytes 8 .. 15: phot_first
-        const long long pf = (long long)(((unsigned long long)v.w << 32) | v.z) + (long long)first[k];
-        v.z = (unsigned)(unsigned long long)pf; v.w = (unsigned)((unsigned long long)pf >> 32);
-    }
-    if (part == 1 && count != nullptr) {                       // bytes 16 .. 23: n_phot
-        const unsigned long long c = (unsigned long long)count[k];
-        v.x = (unsigned)c; v.y = (unsigned)(c >> 32);
-    }
-    if (part == 10) v.w = bf_state ? (unsigned)bf_state[k] : 0u;   // bytes 172 .. 175: bf_state
-    if (part == 9) v.z &= ~(unsigned)clear_flags;                  // bytes 152 .. 155: flags
-    ((uint4*)(dst + k))[part] = v;
-}
 
 // ---------------- host side of the C-ABI ----------------
 // ---- which photon kernel a launch gets: one selector, one table of instantiations ----
@@ -3430,1088 +2665,14 @@ int ims_sensor_fold_delta(const ims_sensor_t* sensor_dev, const ims_sensor_t* se
     return IMS_OK;
 }
 
-// library events of RECORD / WAIT items (one process per GPU)
-static int plan_event(int number, hipEvent_t* out)
-{
-    static std::unordered_map<int, hipEvent_t> evs;
-    if (number < 0 || number > 65535) return set_err(IMS_ERR_ARG, "plan event number out of range");
-    std::lock_guard<std::mutex> lock(g_state_mutex);
-    auto it = evs.find(number);
-    if (it == evs.end()) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        it = evs.emplace(number, e).first;
-    }
-    *out = it->second;
-    return IMS_OK;
-}
-
-// objects of a table sorted by photon count (descending) that have more than `threshold` photons
-static int32_t count_above(const int64_t* n_phot, int32_t n, int64_t threshold)
-{
-    int32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) / 2;
-        if (n_phot[mid] > threshold) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// tiles of the chain's regions that go on after round `round` (the objects with photons beyond it)
-static int64_t tiles_going_on(const ims_chain_t& ch, int32_t round, int32_t nrecalc)
-{
-    const int32_t n_cont = count_above(ch.n_phot, ch.n_objects, (int64_t)(round + 1) * nrecalc);
-    return n_cont > 0 ? ch.tile_prefix_host[n_cont] : 0;
-}
-
-// IMS_PLAN_ROUNDS: the rounds of several chain classes, enqueued round by round so that every chain advances at the same pace
-static int run_rounds(const ims_chain_t* chains, int32_t n_chains, const ims_sensor_t* sensor_dev, const ims_sensor_t* sensor_host,
-                      unsigned char* changed_dev, void* const* streams, int32_t n_streams)
-{
-    if (!chains || n_chains < 0 || n_chains > IMS_MAX_CHAINS) return set_err(IMS_ERR_ARG, "chains is NULL or too many chains");
-    int32_t max_rounds = 0;
-    for (int32_t c = 0; c < n_chains; ++c) {
-        const ims_chain_t& ch = chains[c];
-        if (!ch.params || !ch.pool || !ch.pool_start || !ch.n_phot || !ch.tile_prefix || !ch.tile_prefix_host)
-            return set_err(IMS_ERR_ARG, "chain: NULL pointer");
-        if (ch.stream < 0 || ch.stream >= n_streams) return set_err(IMS_ERR_ARG, "chain stream index out of range");
-        if (ch.nrecalc <= 0 || ch.n_rounds < 0 || ch.n_objects < 0 || ch.n_objects > ch.params->n_objects)
-            return set_err(IMS_ERR_ARG, "chain: nrecalc / n_rounds / n_objects out of range");
-        if (ch.n_edges < 0 || ch.n_edges > IMS_MAX_CHAIN_EDGES) return set_err(IMS_ERR_ARG, "chain: too many edges");
-        for (int32_t k = 1; k < ch.n_objects; ++k)
-            if (ch.n_phot[k] > ch.n_phot[k - 1]) return set_err(IMS_ERR_ARG, "chain: objects must be sorted by photon count, brightest first");
-        if (ch.n_rounds > max_rounds) max_rounds = ch.n_rounds;
-    }
-    for (int32_t r = 0; r < max_rounds; ++r) {
-        for (int32_t c = 0; c < n_chains; ++c) {
-            const ims_chain_t& ch = chains[c];
-            if (r >= ch.n_rounds) continue;
-            void* st = streams[ch.stream];
-            for (int32_t j = 1; j < ch.n_edges; ++j)
-                if (ch.edges[j] == r) {
-                    hipEvent_t e;
-                    const int rc = plan_event(ch.ev_base + j, &e);
-                    if (rc) return rc;
-                    HIP_TRY(hipStreamWaitEvent((hipStream_t)st, e, 0));
-                }
-            const int32_t n_act = count_above(ch.n_phot, ch.n_objects, (int64_t)r * ch.nrecalc);
-            if (n_act == 0) continue;
-            const uint32_t tag = ch.use_tags ? (uint32_t)(r % 255 + 1) : 0u;       // marks the tiles this round's charge lands in
-            // (the varying fields are set in a copy that is only read on the host: the launch takes the compact argument block)
-            ims_render_params_t P = *ch.params;
-            P.bf_tag = tag;
-            P.bf_slot_shift = 0u;
-            int rc = accumulate_round_compact(&P, ch.pool, ch.pool_start, r, ch.nrecalc, n_act, sensor_host ? sensor_host->num_vertices : 0, st);
-            if (rc) return rc;
-            const int32_t n_cont = count_above(ch.n_phot, ch.n_objects, (int64_t)(r + 1) * ch.nrecalc);
-            if (n_cont > 0) {
-                rc = ims_sensor_update_distortions(sensor_dev, sensor_host, ch.first_slot, n_cont, ch.tile_prefix,
-                                                   ch.tile_prefix_host[n_cont], changed_dev, tag, st);
-                if (rc) return rc;
-            }
-        }
-    }
-    return IMS_OK;
-}
-
-int ims_run_plan(const ims_plan_item_t* items, int64_t n_items, const ims_sensor_t* sensor_dev,
-                 const ims_sensor_t* sensor_host, unsigned char* changed_dev, void* const* streams, int32_t n_streams)
-{
-    if (!items && n_items > 0) return set_err(IMS_ERR_ARG, "items is NULL");
-    if (!streams || n_streams <= 0) return set_err(IMS_ERR_ARG, "streams is NULL");
-    for (int64_t k = 0; k < n_items; ++k)
-        if (items[k].stream < 0 || items[k].stream >= n_streams) return set_err(IMS_ERR_ARG, "plan item stream index out of range");
-    for (int64_t k = 0; k < n_items; ++k) {
-        const ims_plan_item_t& it = items[k];
-        void* st = streams[it.stream];
-        int rc = IMS_OK;
-        switch (it.kind) {
-        case IMS_PLAN_RENDER:     rc = ims_shoot_accumulate(it.params, st); break;
-        case IMS_PLAN_SHOOT_POOL: rc = ims_shoot_ops_photons(it.params, it.aux, it.pool, st); break;
-        case IMS_PLAN_ACC_POOL:   rc = ims_accumulate_segments(it.params, it.pool, it.aux, sensor_host ? sensor_host->num_vertices : 0, st); break;
-        case IMS_PLAN_UPDATE:     rc = ims_sensor_update_distortions(sensor_dev, sensor_host, it.first_slot, it.n_slots, it.aux,
-                                                                     it.n_tiles, changed_dev, it.tag, st); break;
-        case IMS_PLAN_INIT:       rc = ims_sensor_init_boundaries(sensor_dev, sensor_host, it.first_slot, it.n_slots, it.aux, it.n_tiles, st); break;
-        case IMS_PLAN_ROUNDS:     rc = run_rounds((const ims_chain_t*)it.aux2, it.n_slots, sensor_dev, sensor_host, changed_dev, streams,
-                                                  n_streams); break;
-        case IMS_PLAN_RECORD:
-        case IMS_PLAN_WAIT: {
-            hipEvent_t e;
-            rc = plan_event(it.n_slots, &e);
-            if (rc) return rc;
-            if (it.kind == IMS_PLAN_RECORD) HIP_TRY(hipEventRecord(e, (hipStream_t)st));
-            else HIP_TRY(hipStreamWaitEvent((hipStream_t)st, e, 0));
-            break; }
-        default: return set_err(IMS_ERR_ARG, "unknown plan item kind");
-        }
-        if (rc) return rc;
-    }
-    return IMS_OK;
-}
-
-// ---- LSST_Image launch planner (csrc/ims_plan.h builds the plan; here: binding to memory, upload, run) ----
-}  // extern "C"
-#include "ims_plan.h"
-
-__global__ __launch_bounds__(256) void k_scatter_add(const int64_t* __restrict__ where, const double* __restrict__ src,
-                                                     double* __restrict__ dst, int64_t n)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n && src[i] != 0.0) unsafeAtomicAdd(dst + where[i], src[i]);
-}
-
-extern "C" {
-
-int ims_plan_lsst_image(const ims_plan_input_t* in, void** plan_out, ims_plan_sizes_t* sizes)
-{
-    if (!in || !plan_out || !sizes) return set_err(IMS_ERR_ARG, "NULL argument");
-    ims_planner::Plan* pl = new ims_planner::Plan();
-    pl->in = *in;
-    const int rc = ims_planner::build(*pl);
-    if (rc) { delete pl; return rc; }
-    // the plan keeps nothing of the caller's arrays
-    pl->in.row = nullptr; pl->in.n_phot = nullptr; pl->in.stamp = nullptr; pl->in.faint = nullptr;
-    *sizes = pl->sizes;
-    *plan_out = pl;
-    return IMS_OK;
-}
-
-int ims_plan_destroy(void* plan)
-{
-    ims_planner::Plan* pl = (ims_planner::Plan*)plan;
-    if (!pl) return IMS_OK;
-    for (hipEvent_t e : pl->events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : pl->d_events) (void)hipEventDestroy(e);
-    delete pl;
-    return IMS_OK;
-}
-
-int ims_plan_bind(void* plan, const ims_render_params_t* base, void* arena_host, void* arena_dev, void* rows_dev,
-                  const ims_object_t* master_dev, double* pool_dev, double* realized_dev)
-{
-    using namespace ims_planner;
-    Plan* pl = (Plan*)plan;
-    if (!pl || !base || !arena_host || !arena_dev || !rows_dev || !master_dev) return set_err(IMS_ERR_ARG, "NULL argument");
-    if (pl->sizes.pool_photons > 0 && !pool_dev) return set_err(IMS_ERR_ARG, "pool_dev is NULL");
-    if (pl->sizes.realized_count > 0 && !realized_dev) return set_err(IMS_ERR_ARG, "realized_dev is NULL");
-    pl->arena_host = (uint8_t*)arena_host; pl->arena_dev = (uint8_t*)arena_dev; pl->rows_dev = (uint8_t*)rows_dev;
-    pl->master_dev = master_dev; pl->pool_dev = pool_dev; pl->realized_dev = realized_dev;
-    std::memcpy(pl->arena_host, pl->arena.data(), pl->arena.size());
-    auto dev = [&](int64_t off) { return off < 0 ? (uint8_t*)nullptr : pl->arena_dev + off; };
-    for (Launch& L : pl->launches) {
-        L.P = *base;
-        L.P.objects = (const ims_object_t*)(pl->rows_dev + L.rows_off);
-        L.P.n_objects = L.n;
-        L.P.seg_prefix = (const int64_t*)dev(L.off_prefix);
-        L.P.n_segments = L.n_segments;
-        L.P.seg_object = (const int32_t*)dev(L.off_segobj);
-        L.P.realized_flux = (L.realized_off >= 0) ? pl->realized_dev + L.realized_off : nullptr;
-        L.P.bf_tag = 0; L.P.bf_slot_shift = 0;
-        L.P.lazy_static = 0;                 // (set again below for the launches that are fused renders: nothing else may carry it)
-    }
-    for (Group& g : pl->groups) {
-        std::memset(&g.pool, 0, sizeof(g.pool));
-        g.pool.n = g.pool_photons;
-        g.pool.converted = 1;
-        const int64_t np = pl->sizes.pool_photons;
-        g.pool.x = pool_dev; g.pool.y = pool_dev ? pool_dev + np : nullptr;
-        g.pool.flux = pool_dev ? pool_dev + 2 * np : nullptr; g.pool.dxdz = pool_dev ? pool_dev + 3 * np : nullptr;
-        g.chain_structs.assign(g.chains.size(), ims_chain_t());
-        for (size_t c = 0; c < g.chains.size(); ++c) {
-            const ChainDesc& ch = g.chains[c];
-            ims_chain_t& cs = g.chain_structs[c];
-            std::memset(&cs, 0, sizeof(cs));
-            const Launch& L = pl->launches[ch.launch];
-            cs.params = &L.P; cs.pool = &g.pool;
-
-            cs.pool_start = (const int64_t*)dev(L.off_pool);
-            cs.n_phot = ch.n_phot.data();
-            cs.tile_prefix = (const int64_t*)dev(ch.off_tile_prefix);
-            cs.tile_prefix_host = ch.tile_prefix_host.data();
-            cs.n_objects = (int32_t)ch.n_phot.size(); cs.first_slot = ch.first_slot; cs.stream = ch.stream; cs.nrecalc = pl->in.nrecalc;
-            cs.n_rounds = ch.n_rounds; cs.use_tags = pl->in.use_tags; cs.ev_base = ch.ev_base; cs.n_edges = (int32_t)ch.edges.size();
-            for (size_t k = 0; k < ch.edges.size(); ++k) cs.edges[k] = ch.edges[k];
-        }
-        g.items.assign(g.steps.size(), ims_plan_item_t());
-        for (size_t k = 0; k < g.steps.size(); ++k) {
-            const Step& s = g.steps[k];
-            ims_plan_item_t& it = g.items[k];
-            std::memset(&it, 0, sizeof(it));
-            it.kind = s.kind; it.stream = s.stream;
-            switch (s.kind) {
-            case IMS_PLAN_RENDER: pl->launches[s.launch].P.lazy_static = base->lazy_static; it.params = &pl->launches[s.launch].P; break;
-            case IMS_PLAN_SHOOT_POOL:
-                it.params = &pl->launches[s.launch].P; it.pool = &g.pool; it.aux = (const int64_t*)dev(pl->launches[s.launch].off_pool); break;
-            case IMS_PLAN_INIT:
-                it.first_slot = s.first_slot; it.n_slots = s.n_slots; it.aux = (const int64_t*)dev(s.off_tile_prefix); it.n_tiles = s.n_tiles; break;
-            case IMS_PLAN_RECORD: it.n_slots = s.event; break;
-            case IMS_PLAN_WAIT: it.n_slots = s.event; break;
-            case IMS_PLAN_ROUNDS: it.n_slots = s.n_chains; it.aux2 = g.chain_structs.data() + s.chain_begin; break;
-            default: return set_err(IMS_ERR_ARG, "planner: unexpected step kind");
-            }
-        }
-    }
-    pl->bound = true; pl->uploaded = false;
-    return IMS_OK;
-}
-
-int ims_plan_upload(void* plan, void* stream)
-{
-    using namespace ims_planner;
-    Plan* pl = (Plan*)plan;
-    if (!pl || !pl->bound) return set_err(IMS_ERR_ARG, "plan is NULL or not bound");
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(pl->arena_dev, pl->arena_host, pl->arena.size(), hipMemcpyHostToDevice, st));
-    for (const Launch& L : pl->launches) {
-        if (L.n <= 0) continue;
-        const int rc = ims_gather_rows(pl->master_dev, (const int64_t*)(pl->arena_dev + L.off_index), (const int64_t*)(pl->arena_dev + L.off_first),
-                                       (const int64_t*)(pl->arena_dev + L.off_count), (const int32_t*)(pl->arena_dev + L.off_bf), 0,
-                                       (ims_object_t*)(pl->rows_dev + L.rows_off), L.n, stream);
-        if (rc) return rc;
-    }
-    pl->uploaded = true;
-    return IMS_OK;
-}
-
-static int plan_enqueue(ims_planner::Plan* pl, ims_sensor_t* sensor_dev, ims_sensor_t* sensor_host, ims_bf_slot_t* slots_dev,
-                        unsigned char* changed_dev, void* main_stream, void* const* streams, int32_t n_streams, int32_t own_work_queued,
-                        bool defer_top = false)
-{
-    using namespace ims_planner;
-    if (!streams || n_streams < 5) return set_err(IMS_ERR_ARG, "streams: five plan streams by role are required");
-    bool any_slots = false;
-    for (const Group& g : pl->groups) any_slots = any_slots || g.n_slots > 0;
-    if (any_slots && (!sensor_dev || !sensor_host || !slots_dev || !changed_dev || !sensor_host->bf_slots))
-        return set_err(IMS_ERR_ARG, "sensor / slot table / changed is NULL");
-    // the rounds of the top chain can be left to a joint run when the plan is ONE group of regions (a later group rewrites the
-    // slot table behind everything queued) in the form the joint kernels take: 4 vertices per edge, qdist 3, regions in place
-    pl->deferred = false;
-    bool defer = defer_top && pl->groups.size() == 1 && pl->groups[0].n_slots > 0 && !pl->groups[0].chain_structs.empty() &&
-                 sensor_host->num_vertices == IT_NV && sensor_host->qdist == 3;
-    if (defer)
-        for (const ims_chain_t& cs : pl->groups[0].chain_structs)
-            defer = defer && cs.first_slot > 0;
-    // distinct streams
-    std::vector<hipStream_t> uniq;
-    for (int k = 0; k < n_streams; ++k)
-        if (std::find(uniq.begin(), uniq.end(), (hipStream_t)streams[k]) == uniq.end()) uniq.push_back((hipStream_t)streams[k]);
-    const size_t need = 2 + 2 * uniq.size();
-    while (pl->events.size() < need) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        pl->events.push_back(e);
-    }
-    hipStream_t main = (hipStream_t)main_stream, chain = (hipStream_t)streams[ROLE_CHAIN];
-    if (pl->realized_dev && pl->sizes.realized_count > 0)
-        HIP_TRY(hipMemsetAsync(pl->realized_dev, 0, (size_t)pl->sizes.realized_count * sizeof(double), main));
-    HIP_TRY(hipEventRecord(pl->events[0], main));
-    for (hipStream_t s : uniq) HIP_TRY(hipStreamWaitEvent(s, pl->events[0], 0));
-    bool queued = own_work_queued != 0;
-    for (size_t gi = 0; gi < pl->groups.size(); ++gi) {
-        Group& g = pl->groups[gi];
-        if (g.n_slots > 0) {
-            const int n0 = pl->in.n_static_slots;
-            if (n0 + g.n_slots > pl->in.slot_capacity) return set_err(IMS_ERR_ARG, "too many brighter-fatter slots");
-            // The slot table is rewritten by a copy on the chain stream: behind everything this renderer has queued on every
-            // stream (a later group's table must not change under the launches of the one before) and ahead of what follows
-            if (queued)
-                for (size_t k = 0; k < uniq.size(); ++k)
-                    if (uniq[k] != chain) {
-                        HIP_TRY(hipEventRecord(pl->events[2 + k], uniq[k]));
-                        HIP_TRY(hipStreamWaitEvent(chain, pl->events[2 + k], 0));
-                    }
-            HIP_TRY(hipMemcpyAsync(slots_dev + n0, pl->arena_host + g.off_slots, (size_t)g.n_slots * sizeof(ims_bf_slot_t),
-                                   hipMemcpyHostToDevice, chain));
-            HIP_TRY(hipMemcpyAsync(&sensor_dev->n_bf_slots, pl->arena_host + pl->off_nslots[gi], sizeof(int32_t), hipMemcpyHostToDevice, chain));
-            HIP_TRY(hipEventRecord(pl->events[1], chain));
-            for (hipStream_t s : uniq) if (s != chain) HIP_TRY(hipStreamWaitEvent(s, pl->events[1], 0));
-            std::memcpy((ims_bf_slot_t*)(uintptr_t)sensor_host->bf_slots + n0, pl->arena_host + g.off_slots, (size_t)g.n_slots * sizeof(ims_bf_slot_t));
-            sensor_host->n_bf_slots = n0 + g.n_slots;
-        }
-        if (defer) {
-            // without the rounds item: the rounds of ALL chain classes are left to joint runs
-            std::vector<ims_plan_item_t> items;
-            for (const ims_plan_item_t& it : g.items)
-                if (it.kind != IMS_PLAN_ROUNDS) items.push_back(it);
-            const int rc = ims_run_plan(items.data(), (int64_t)items.size(), sensor_dev, sensor_host, changed_dev, streams, n_streams);
-            if (rc) return rc;
-        } else {
-            const int rc = ims_run_plan(g.items.data(), (int64_t)g.items.size(), sensor_dev, sensor_host, changed_dev, streams, n_streams);
-            if (rc) return rc;
-        }
-        queued = true;
-    }
-    if (defer_top) {
-        // no join yet (ims_plan_join): where this plan's work ends on every stream is recorded NOW -- on streams shared by role the
-        // next CCD's work follows, and a join must not wait for that
-        for (size_t k = 0; k < uniq.size(); ++k) HIP_TRY(hipEventRecord(pl->events[2 + uniq.size() + k], uniq[k]));
-        pl->unjoined = (int)uniq.size();
-        pl->deferred = defer;
-        pl->left = defer ? ((1u << pl->groups[0].chain_structs.size()) - 1u) : 0u;
-        pl->d_done_used = 0;
-        pl->d_sensor_dev = sensor_dev; pl->d_sensor_host = sensor_host; pl->d_changed = changed_dev; pl->d_main = main_stream;
-        pl->d_streams.assign(streams, streams + n_streams);
-        return IMS_OK;
-    }
-    for (size_t k = 0; k < uniq.size(); ++k) {
-        HIP_TRY(hipEventRecord(pl->events[2 + uniq.size() + k], uniq[k]));
-        HIP_TRY(hipStreamWaitEvent(main, pl->events[2 + uniq.size() + k], 0));
-    }
-    return IMS_OK;
-}
-
-// (Two other forms of this call were built, measured in round 4 and removed in round 5: the whole enqueue captured into a
-// hipGraph -- capture + instantiate + launch of a CCD's ~3 000-node plan cost the host 51 ms against 24 ms for enqueueing it, and a
-// graph does not run on the caller's streams -- and one plan's rounds through the joint runner with its tile lists -- a fourth
-// dependent launch per round on a chain of 185 rounds: C3 24.2 -> 25.2 ms without lists, 33 ms with them.)
-int ims_plan_run(void* plan, ims_sensor_t* sensor_dev, ims_sensor_t* sensor_host, ims_bf_slot_t* slots_dev, unsigned char* changed_dev,
-                 void* main_stream, void* const* streams, int32_t n_streams, int32_t own_work_queued)
-{
-    using namespace ims_planner;
-    Plan* pl = (Plan*)plan;
-    if (!pl || !pl->uploaded) return set_err(IMS_ERR_ARG, "plan is NULL or not uploaded");
-    return plan_enqueue(pl, sensor_dev, sensor_host, slots_dev, changed_dev, main_stream, streams, n_streams, own_work_queued);
-}
-
-int ims_plan_join(void* plan, void* stream)
-{
-    using namespace ims_planner;
-    Plan* pl = (Plan*)plan;
-    if (!pl) return set_err(IMS_ERR_ARG, "plan is NULL");
-    if (pl->deferred) return set_err(IMS_ERR_ARG, "ims_plan_join: the rounds left by ims_plan_run_deferred have not been run (ims_plans_run_joint)");
-    hipStream_t st = (hipStream_t)stream;
-    for (int k = 0; k < pl->unjoined; ++k) HIP_TRY(hipStreamWaitEvent(st, pl->events[2 + (size_t)pl->unjoined + k], 0));
-    for (size_t k = 0; k < pl->d_done_used; ++k) HIP_TRY(hipStreamWaitEvent(st, pl->d_events[4 + k], 0));
-    pl->unjoined = 0; pl->d_done_used = 0;
-    return IMS_OK;
-}
-
-int ims_plan_run_deferred(void* plan, ims_sensor_t* sensor_dev, ims_sensor_t* sensor_host, ims_bf_slot_t* slots_dev, unsigned char* changed_dev,
-                          void* main_stream, void* const* streams, int32_t n_streams, int32_t own_work_queued, int32_t* deferred)
-{
-    using namespace ims_planner;
-    Plan* pl = (Plan*)plan;
-    if (!pl || !pl->uploaded) return set_err(IMS_ERR_ARG, "plan is NULL or not uploaded");
-    if (!deferred) return set_err(IMS_ERR_ARG, "deferred is NULL");
-    const int rc = plan_enqueue(pl, sensor_dev, sensor_host, slots_dev, changed_dev, main_stream, streams, n_streams, own_work_queued, true);
-    *deferred = (rc == IMS_OK && pl->deferred) ? (int32_t)pl->groups[0].chain_structs.size() : 0;
-    return rc;
-}
-
-int ims_plans_run_joint(void* const* plans, int32_t n_plans, void* joint_stream, int32_t first_chain, int32_t n_chains)
-{
-    using namespace ims_planner;
-    if (n_plans < 0 || (n_plans > 0 && !plans)) return set_err(IMS_ERR_ARG, "plans is NULL");
-    if (first_chain < 0 || n_chains < 1) return set_err(IMS_ERR_ARG, "joint run: chain range");
-    struct Act { Plan* pl; const ims_chain_t* ch; int chain; hipEvent_t done; };
-    std::vector<Act> act;
-    hipStream_t js = (hipStream_t)joint_stream;
-    // what an error return has to undo: the done events handed out below (a plan's join must not wait for a record that
-    // never comes) and the ring entry held while this call enqueues (its event is recorded all the same: launches that
-    // did go out read the entry's tables)
-    struct Undo {
-        std::vector<Plan*> counted; bool* busy = nullptr; hipEvent_t table_event = nullptr; hipStream_t js = nullptr; bool ok = false;
-        ~Undo() {
-            if (!ok) for (Plan* p : counted) if (p->d_done_used > 0) --p->d_done_used;
-            if (busy) {
-                if (!ok && table_event) (void)hipEventRecord(table_event, js);
-                std::lock_guard<std::mutex> lock(g_state_mutex);
-                *busy = false;
-            }
-        }
-    } undo;
-    undo.js = js;
-    for (int32_t k = 0; k < n_plans; ++k) {
-        Plan* pl = (Plan*)plans[k];
-        if (!pl) return set_err(IMS_ERR_ARG, "plans: NULL entry");
-        if (!pl->deferred) continue;                       // ran whole (no bright object, several groups): nothing left to do
-        const int nc = (int)pl->groups[0].chain_structs.size();
-        bool any = false;
-        for (int c = first_chain; c < first_chain + n_chains && c < nc; ++c)
-            if (pl->left & (1u << c)) { act.push_back({ pl, &pl->groups[0].chain_structs[c], c, nullptr }); any = true; }
-        if (!any) continue;
-        // own events: four "chain stream ready", then one per joint run since the last join
-        while (pl->d_events.size() < 4 + pl->d_done_used + 1) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            pl->d_events.push_back(e);
-        }
-        const hipEvent_t done = pl->d_events[4 + pl->d_done_used++];
-        undo.counted.push_back(pl);
-        for (Act& a : act) if (a.pl == pl) a.done = done;
-    }
-    if (act.empty()) { undo.ok = true; return IMS_OK; }
-    if ((int)act.size() > IMS_JOINT_MAX) return set_err(IMS_ERR_ARG, "at most 64 chains per joint run");
-    const int32_t nrecalc = act[0].ch->nrecalc, use_tags = act[0].ch->use_tags;
-    int32_t max_rounds = 0;
-    for (const Act& a : act) {
-        const ims_chain_t& ch = *a.ch;
-        if (ch.nrecalc != nrecalc || ch.use_tags != use_tags) return set_err(IMS_ERR_ARG, "joint run: the plans differ in nrecalc / tile tags");
-        if (!ch.params || !ch.pool || !ch.pool->converted || !ch.pool_start || !ch.params->objects || !ch.params->image)
-            return set_err(IMS_ERR_ARG, "joint run: chain without table / pool / image");
-        if (ch.n_rounds > max_rounds) max_rounds = ch.n_rounds;
-        // the joint stream takes over behind the chain's own stream (the regions' initial state, the first pool slice)
-        // (behind the END OF THE CCD'S OWN FRONT on that stream -- the event ims_plan_run_deferred recorded there -- not behind
-        // whatever the stream holds by now: the joint run may be enqueued from a second host thread while the fronts of the
-        // next batch of CCDs are already being queued on the shared streams, and the chain must not wait for those)
-        hipStream_t cs = (hipStream_t)a.pl->d_streams[ch.stream];
-        if (cs != js) {
-            std::vector<hipStream_t> uniq;
-            for (void* st : a.pl->d_streams)
-                if (std::find(uniq.begin(), uniq.end(), (hipStream_t)st) == uniq.end()) uniq.push_back((hipStream_t)st);
-            const size_t k = (size_t)(std::find(uniq.begin(), uniq.end(), cs) - uniq.begin());
-            if ((int)uniq.size() != a.pl->unjoined || k >= uniq.size())
-                return set_err(IMS_ERR_ARG, "joint run: the plan was not enqueued by ims_plan_run_deferred on these streams");
-            HIP_TRY(hipStreamWaitEvent(js, a.pl->events[2 + uniq.size() + k], 0));
-        }
-    }
-    const int32_t segs = (nrecalc + 255) / 256;
-    const long long dpp_max_tiles = g_tune.upd_dpp_max;
-    // the per-chain argument blocks in device memory, one table per joint run out of a ring (a table is read until the run's
-    // last round: the ring's event says when)
-    // active-tile lists (k_build_active_j): on for rounds of more than list_min_tiles tiles; joint_lists = 0: the full sweeps
-    const bool lists_on = g_tune.joint_lists != 0;
-    const long long list_min_tiles = g_tune.joint_list_min;
-    const double list_fraction = g_tune.active_fraction;
-    int64_t tiles_max = 0;                                   // round 0 has them all
-    for (const Act& a : act) tiles_max += tiles_going_on(*a.ch, 0, nrecalc);
-    const bool lists = lists_on && tiles_max > list_min_tiles;
-    struct Ring { JointTables* dev; hipEvent_t free_after; bool used; bool busy; unsigned long long* upd; unsigned long long* ref; int* count; int64_t cap;
-                  JointRound* rounds_dev; JointRound* rounds_pin; int64_t rounds_cap; unsigned int* words; };
-    // one ring per DEVICE (its tables live in that device's memory: one process per GPU is the rule, but a process that holds
-    // two devices must not hand the second one the first one's tables)
-    static std::map<int, std::pair<std::vector<Ring>, size_t>> rings;
-    int device_now = 0;
-    HIP_TRY(hipGetDevice(&device_now));
-    JointTables* tables_dev = nullptr;
-    JointRound* rounds_dev = nullptr;
-    JointRound* rounds_pin = nullptr;
-    hipEvent_t table_event = nullptr;
-    JointLists Ls{ nullptr, nullptr, nullptr };
-    unsigned int* words_dev = nullptr;
-    // search-side lists (TileLister): the pixel search appends the tiles, no builder launch
-    const bool search_lists = lists && g_tune.joint_search_lists != 0;
-    {
-        std::lock_guard<std::mutex> lock(g_state_mutex);
-        std::vector<Ring>& ring = rings[device_now].first;
-        size_t& ring_next = rings[device_now].second;
-        if (ring.empty()) {
-            JointTables* block = nullptr;
-            int* counts = nullptr;
-            HIP_TRY(hipMalloc((void**)&block, 64 * sizeof(JointTables)));
-            HIP_TRY(hipMalloc((void**)&counts, 64 * 4 * sizeof(int)));
-            for (int k = 0; k < 64; ++k) {
-                Ring r{ block + k, nullptr, false, false, nullptr, nullptr, counts + 4 * k, 0, nullptr, nullptr, 0, nullptr };
-                HIP_TRY(hipEventCreateWithFlags(&r.free_after, hipEventDisableTiming));
-                ring.push_back(r);
-            }
-        }
-        // an entry another thread is still enqueueing with (its event not yet recorded) is passed over
-        size_t tries = 0;
-        while (ring[ring_next % ring.size()].busy && tries++ < ring.size()) ++ring_next;
-        Ring& r = ring[ring_next++ % ring.size()];
-        if (r.busy) return set_err(IMS_ERR_ARG, "joint run: all 64 table entries are being enqueued with");
-        if (r.used) HIP_TRY(hipEventSynchronize(r.free_after));
-        r.used = true; r.busy = true;
-        undo.busy = &r.busy; undo.table_event = r.free_after;
-        if (lists && r.cap < tiles_max) {
-            // (a growth is a device-wide synchronisation: the capacity is kept and rounded up generously)
-            if (r.upd) { HIP_TRY(hipFree(r.upd)); HIP_TRY(hipFree(r.ref)); HIP_TRY(hipFree(r.words)); }
-            r.cap = tiles_max + tiles_max / 2 + 65536;
-            HIP_TRY(hipMalloc((void**)&r.upd, (size_t)r.cap * sizeof(unsigned long long)));
-            HIP_TRY(hipMalloc((void**)&r.ref, (size_t)r.cap * sizeof(unsigned long long)));
-            HIP_TRY(hipMalloc((void**)&r.words, (size_t)r.cap * sizeof(unsigned int)));
-        }
-        if (r.rounds_cap < max_rounds) {
-            // the round tables of the run: a page-locked staging buffer and its device copy (grown rarely: capacity kept)
-            if (r.rounds_dev) { HIP_TRY(hipFree(r.rounds_dev)); HIP_TRY(hipHostFree(r.rounds_pin)); }
-            r.rounds_cap = max_rounds + max_rounds / 2 + 64;
-            HIP_TRY(hipMalloc((void**)&r.rounds_dev, (size_t)r.rounds_cap * sizeof(JointRound)));
-            HIP_TRY(hipHostMalloc((void**)&r.rounds_pin, (size_t)r.rounds_cap * sizeof(JointRound), hipHostMallocDefault));
-        }
-        tables_dev = r.dev; table_event = r.free_after;
-        Ls.upd = r.upd; Ls.ref = r.ref; Ls.count = r.count;
-        words_dev = r.words;
-        rounds_dev = r.rounds_dev; rounds_pin = r.rounds_pin;
-    }
-    if (lists) HIP_TRY(hipMemsetAsync(Ls.count, 0, 4 * sizeof(int), js));
-    if (search_lists) HIP_TRY(hipMemsetAsync(words_dev, 0, (size_t)tiles_max * sizeof(unsigned int), js));
-    // a chain's tile words: behind those of the chains before it (round 0 lists from all the regions that go on)
-    std::vector<int64_t> word_off(act.size() + 1, 0);
-    for (size_t k = 0; k < act.size(); ++k) word_off[k + 1] = word_off[k] + tiles_going_on(*act[k].ch, 0, nrecalc);
-    bool dpp_ok = true;
-    for (size_t k0 = 0; k0 < act.size(); k0 += JOINT_CHUNK) {
-        JointChunk Ck;
-        std::memset(&Ck, 0, sizeof(Ck));
-        for (size_t k = 0; k < (size_t)JOINT_CHUNK; ++k) {
-            const Act& a = act[k0 + k < act.size() ? k0 + k : 0];         // entries beyond the last repeat chain 0 (never selected: zero width)
-            const ims_chain_t& ch = *a.ch;
-            Ck.a[k] = round_args(*ch.params, *ch.pool);
-            Ck.a[k].bf_tag = 0; Ck.a[k].bf_slot_shift = 0;                    // (the launch brings the round's tag)
-            Ck.pool_start[k] = ch.pool_start;
-            Ck.sp[k] = a.pl->d_sensor_dev; Ck.tile_prefix[k] = ch.tile_prefix; Ck.changed[k] = a.pl->d_changed;
-            Ck.dl[k] = a.pl->d_sensor_host->bf_dl; Ck.first_slot[k] = ch.first_slot;
-            Ck.words[k] = (search_lists && k0 + k < act.size()) ? words_dev + word_off[k0 + k] : nullptr;
-            dpp_ok = dpp_ok && a.pl->d_sensor_host->bf_dl != nullptr;
-        }
-        hipLaunchKernelGGL(k_store_joint_tables, dim3(1), dim3(64), 0, js, Ck, tables_dev, (int)k0);
-        HIP_TRY(hipGetLastError());
-    }
-    // every round's tables (workgroup / tile ends per chain) in one pass on the host, ONE copy to the device; per round the
-    // launches then take a pointer
-    struct RoundTotals { int64_t wgs, tiles, build_wgs; };
-    std::vector<RoundTotals> totals((size_t)max_rounds);
-    for (int32_t r = 0; r < max_rounds; ++r) {
-        JointRound& R = rounds_pin[r];
-        int64_t wgs = 0, tiles = 0, build_wgs = 0;
-        for (int k = 0; k < IMS_JOINT_MAX; ++k) {
-            int32_t n_act = 0, n_cont = 0;
-            int64_t tk = 0;
-            if (k < (int)act.size() && r < act[k].ch->n_rounds) {
-                const ims_chain_t& ch = *act[k].ch;
-                n_act = count_above(ch.n_phot, ch.n_objects, (int64_t)r * nrecalc);
-                n_cont = count_above(ch.n_phot, ch.n_objects, (int64_t)(r + 1) * nrecalc);
-                tk = tiles_going_on(ch, r, nrecalc);
-            }
-            tiles += tk;
-            build_wgs += (tk + 255) / 256;
-            wgs += (int64_t)n_act * segs;
-            if (wgs > 0x7fffffffLL || tiles > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "joint run: too many workgroups for one round");
-            R.ea.v[k] = (int32_t)wgs; R.eu.v[k] = (int32_t)tiles; R.ns.v[k] = n_cont > 0 ? n_cont : 1;
-            R.ewg.v[k] = (int32_t)build_wgs; R.tof.v[k] = (int32_t)tk;
-        }
-        totals[(size_t)r] = { wgs, tiles, build_wgs };
-    }
-    if (max_rounds > 0)
-        HIP_TRY(hipMemcpyAsync(rounds_dev, rounds_pin, (size_t)max_rounds * sizeof(JointRound), hipMemcpyHostToDevice, js));
-    // the round after which a CCD's chains of this run are through (its longest chain)
-    std::vector<std::pair<int32_t, hipEvent_t>> done_at;
-    for (size_t k = 0; k < act.size(); ++k) {
-        bool first_of_plan = true;
-        int32_t last = 0;
-        for (size_t j = 0; j < act.size(); ++j)
-            if (act[j].pl == act[k].pl) { if (j < k) first_of_plan = false; if (act[j].ch->n_rounds > last) last = act[j].ch->n_rounds; }
-        if (first_of_plan) done_at.push_back({ last - 1, act[k].done });
-    }
-    for (int32_t r = 0; r < max_rounds; ++r) {
-        for (const Act& a : act) {
-            const ims_chain_t& ch = *a.ch;
-            if (r >= ch.n_rounds) continue;
-            for (int32_t j = 1; j < ch.n_edges; ++j)
-                if (ch.edges[j] == r) {
-                    hipEvent_t e;
-                    const int rc = plan_event(ch.ev_base + j, &e);
-                    if (rc) return rc;
-                    HIP_TRY(hipStreamWaitEvent(js, e, 0));
-                }
-        }
-        const uint32_t tag = (use_tags || lists) ? (uint32_t)(r % 255 + 1) : 0u;
-        const int64_t wgs = totals[(size_t)r].wgs, tiles = totals[(size_t)r].tiles, build_wgs = totals[(size_t)r].build_wgs;
-        const JointRound* R = rounds_dev + r;
-        const bool list_round = tiles > 0 && lists && tiles > list_min_tiles;
-        const int parity_r = r & 1;
-        if (wgs > 0) {
-            LaunchTimer tm(js, 4);
-            const bool sl = search_lists && list_round;
-            hipLaunchKernelGGL((k_accumulate_round_j<4, 256>), dim3((unsigned)wgs), dim3(256), 0, js, (const JointAcc*)&tables_dev->acc, R, tag,
-                               (int64_t)r * nrecalc, nrecalc, segs, sl ? Ls.upd : (unsigned long long*)nullptr,
-                               sl ? Ls.count + 2 * parity_r : (int*)nullptr, (unsigned int)(r + 1));
-        }
-        if (list_round) {
-            // marks -> lists -> the update and the refresh over the listed tiles (a launch of a fraction of the tiles walks them)
-            const JointUpd* U = &tables_dev->upd;
-            const int parity = r & 1;
-            int64_t grid = (int64_t)((double)tiles * list_fraction);
-            if (grid < 256 && list_fraction >= 0.05) grid = 256;
-            if (grid < 1) grid = 1;
-            if (grid > tiles) grid = tiles;
-            if (!search_lists)
-                hipLaunchKernelGGL(k_build_active_j, dim3((unsigned)build_wgs), dim3(256), 0, js, U, R, tag, Ls, parity, (int)g_tune.joint_fine_marks);
-            hipLaunchKernelGGL((k_update_list_j<4, false>), dim3((unsigned)grid), dim3(256), 0, js, U, Ls, parity, tag, search_lists ? 1 : 0);
-            hipLaunchKernelGGL(k_refresh_list_j<4>, dim3((unsigned)grid), dim3(256), 0, js, U, Ls, parity, tag, search_lists ? 1 : 0);
-        } else if (tiles > 0) {
-            const JointUpd* U = &tables_dev->upd;
-            const bool dpp = dpp_ok && g_tune.upd_dpp && tiles <= dpp_max_tiles;
-            if (dpp) hipLaunchKernelGGL((k_update_distortions_q3_j<4, true>), dim3((unsigned)tiles), dim3(256), 0, js, U, R, tag);
-            else hipLaunchKernelGGL((k_update_distortions_q3_j<4, false>), dim3((unsigned)tiles), dim3(256), 0, js, U, R, tag);
-            hipLaunchKernelGGL(k_refresh_changed_j<4>, dim3((unsigned)tiles), dim3(256), 0, js, U, R, tag);
-        }
-#ifdef IMS_EXTRA_LAUNCHES
-        for (int xl = 0; xl < IMS_EXTRA_LAUNCHES; ++xl) hipLaunchKernelGGL(k_nop, dim3(1), dim3(64), 0, js, (int*)nullptr);
-#endif
-        // a CCD's chains of this run are through with the longest of them
-        for (const auto& d : done_at)
-            if (d.first == r) HIP_TRY(hipEventRecord(d.second, js));
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(table_event, js));
-    undo.ok = true;
-    for (const Act& a : act) {
-        a.pl->left &= ~(1u << a.chain);
-        if (a.pl->left == 0u) a.pl->deferred = false;
-    }
-    return IMS_OK;
-}
-
-int ims_plan_add_realized(void* plan, double* out_dev, void* stream)
-{
-    using namespace ims_planner;
-    Plan* pl = (Plan*)plan;
-    if (!pl || !pl->uploaded) return set_err(IMS_ERR_ARG, "plan is NULL or not uploaded");
-    const int64_t n = pl->sizes.realized_count;
-    if (n <= 0) return IMS_OK;
-    if (!out_dev) return set_err(IMS_ERR_ARG, "out_dev is NULL");
-    hipLaunchKernelGGL(k_scatter_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const int64_t*)(pl->arena_dev + pl->off_realized_where), (const double*)pl->realized_dev, out_dev, n);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
 }  // extern "C"
 
-// ---- the inverse transforms of the FFT branch (hipFFT, plans cached) ----
-__global__ __launch_bounds__(256) void k_scale(double* __restrict__ v, int64_t n, double s)
-{
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) v[i] = v[i] * s;
-}
-
-extern "C" {
-
-static int fft_err(hipfftResult r, const char* what)
-{
-    if (r == HIPFFT_SUCCESS) return IMS_OK;
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: hipfft error %d", what, (int)r);
-    return set_err(IMS_ERR_HIP, buf);
-}
-
-// Plans are kept per (size, stream) and transform ONE stamp: a batch is a loop over it.  The FIRST plan of a process costs seconds
-// (measured in round 5 on a fresh box: 2.4 s for the first call -- hipFFT / rocFFT start up and compile their kernels at run time
-// --, 0.5 s for the next new size, nothing after that; with a plan per size AND batch count every new combination paid again: 2.8
-// of the 3.4 s a fresh process spent on its first 48 CCDs), a CCD holds one to three FFT-drawn objects of a handful of sizes, and
-// a transform of 1024^2 or more fills the device by itself, so nothing is lost by not batching.  Per STREAM because a plan owns
-// its work buffer (the transposes of the large sizes go through it): the same plan executing on two streams at once -- the FFT
-// objects of two CCDs of a focal plane on the two top-chain streams -- would share it.  Small transforms (below 1024^2:
-// launch-bound) keep batched plans.  ims_fft_warm makes the plans ahead of time (from another host thread, while the host
-// still reads catalogs).
-
-// the plan of (nfft, per_plan, stream): looked up under the lock, MADE outside it (seconds for a size's first plan: plans of
-// different sizes are made side by side by ims_fft_warm's callers), entered under the lock again
-static int fft_plan_get(const ims_libs::Fft* F, int32_t nfft, int64_t per_plan, void* stream, hipfftHandle* out)
-{
-    const std::tuple<int32_t, int64_t, void*> key(nfft, per_plan, stream);
-    {
-        std::lock_guard<std::mutex> lock(g_fft_mutex);
-        auto it = g_fft_plans.find(key);
-        if (it != g_fft_plans.end()) { *out = it->second; return IMS_OK; }
-    }
-    int n[2] = { nfft, nfft };
-    int inembed[2] = { nfft, nfft / 2 + 1 }, onembed[2] = { nfft, nfft };
-    hipfftHandle p;
-    int rc = fft_err(F->plan_many(&p, 2, n, inembed, 1, nfft * (nfft / 2 + 1), onembed, 1, nfft * nfft, HIPFFT_Z2D, (int)per_plan),
-                     "hipfftPlanMany");
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(g_fft_mutex);
-    auto ins = g_fft_plans.emplace(key, p);
-    if (!ins.second) (void)F->destroy(p);            // another thread was faster
-    *out = ins.first->second;
-    return IMS_OK;
-}
-
-int ims_fft_warm(int32_t nfft, void* stream)
-{
-    if (nfft < 2 || (nfft & 1)) return set_err(IMS_ERR_ARG, "nfft must be even and >= 2");
-    const ims_libs::Fft* F = ims_libs::fft();
-    if (!F) return set_err(IMS_ERR_UNSUPPORTED, "hipFFT is not loadable (libhipfft.so; IMS_HIPFFT_LIB names a file)");
-    hipfftHandle plan;
-    return fft_plan_get(F, nfft, 1, stream, &plan);
-}
-
-static int fft_inverse_impl(double* kbuf_dev, double* rbuf_dev, int32_t nfft, int64_t batch, void* stream, bool normalise)
-{
-    if (batch <= 0) return IMS_OK;
-    if (!kbuf_dev || !rbuf_dev) return set_err(IMS_ERR_ARG, "NULL buffer");
-    if (nfft < 2 || (nfft & 1) || batch > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "nfft must be even and >= 2");
-    const ims_libs::Fft* F = ims_libs::fft();
-    if (!F) return set_err(IMS_ERR_UNSUPPORTED, "hipFFT is not loadable (libhipfft.so; IMS_HIPFFT_LIB names a file)");
-    int64_t per_plan = nfft >= 1024 ? 1 : batch;
-    {
-        if (per_plan != batch) {
-            // a (size, batch) pair that comes again -- a replayed step, the same counts on many CCDs -- gets its batched plan (a few
-            // milliseconds once the size's kernels exist: only a size's FIRST plan is expensive)
-            static std::map<std::tuple<int32_t, int64_t, void*>, int> asked;
-            std::lock_guard<std::mutex> lock(g_fft_mutex);
-            if (++asked[std::make_tuple(nfft, batch, stream)] >= 2) per_plan = batch;
-        }
-        hipfftHandle plan;
-        int rc = fft_plan_get(F, nfft, per_plan, stream, &plan);
-        if (rc) return rc;
-        // (set-stream + execute of one plan must not interleave between host threads: a plan carries its stream)
-        static std::mutex exec_mutex;
-        std::lock_guard<std::mutex> lock(exec_mutex);
-        rc = fft_err(F->set_stream(plan, (hipStream_t)stream), "hipfftSetStream");
-        if (rc) return rc;
-        for (int64_t b = 0; b < batch; b += per_plan) {
-            rc = fft_err(F->exec_z2d(plan, (hipfftDoubleComplex*)kbuf_dev + b * (int64_t)nfft * (nfft / 2 + 1),
-                                     (hipfftDoubleReal*)rbuf_dev + b * (int64_t)nfft * nfft), "hipfftExecZ2D");
-            if (rc) return rc;
-        }
-    }
-    if (!normalise) return IMS_OK;          // the readers multiply (ims_fft_params_t.rbuf_raw)
-    // numpy / GalSim normalisation of the inverse ("backward": 1 / N^2): exact for the even sizes used (powers of two)
-    const int64_t total = batch * (int64_t)nfft * nfft;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_scale, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rbuf_dev, total, 1.0 / ((double)nfft * (double)nfft));
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_fft_inverse(double* kbuf_dev, double* rbuf_dev, int32_t nfft, int64_t batch, void* stream)
-{
-    return fft_inverse_impl(kbuf_dev, rbuf_dev, nfft, batch, stream, true);
-}
-
-int ims_fft_inverse_raw(double* kbuf_dev, double* rbuf_dev, int32_t nfft, int64_t batch, void* stream)
-{
-    return fft_inverse_impl(kbuf_dev, rbuf_dev, nfft, batch, stream, false);
-}
-
-// a workgroup's share of the elements of an elementwise FFT kernel (walk_span): at least 4 096 workgroups where the elements allow it
-// (256 CUs x 16), at most 8 192 elements each (32 passes per lookup of the object; short enough that a star's core rows, where a
-// pixel costs many times a pixel of the wings, spread over many workgroups)
-struct FftSpan { int64_t span; unsigned grid; };
-static FftSpan fft_span(int64_t n)
-{
-    int64_t span = ((n + 4095) / 4096 + 255) / 256 * 256;
-    if (span < 256) span = 256;
-    if (span > 8192) span = 8192;
-    return { span, (unsigned)((n + span - 1) / span) };
-}
-
-int ims_fft_kspace_fill(const ims_fft_params_t* params, const ims_fft_object_t* objects_dev, int64_t n_objects,
-                        const int64_t* elem_prefix_dev, int64_t n_elems, double* kbuf, void* stream)
-{
-    if (!params || !objects_dev || !elem_prefix_dev || !kbuf) return set_err(IMS_ERR_ARG, "NULL argument");
-    if (params->n_kpsf < 0 || params->n_kpsf > IMS_MAX_PSF) return set_err(IMS_ERR_ARG, "n_kpsf out of range");
-    if (n_objects <= 0 || n_elems <= 0) return IMS_OK;
-    {
-        LaunchTimer tm((hipStream_t)stream, 3);
-        const FftSpan sp = fft_span(n_elems);
-        hipLaunchKernelGGL(k_fft_kspace_fill, dim3(sp.grid), dim3(256), 0, (hipStream_t)stream, *params, objects_dev,
-                           n_objects, elem_prefix_dev, n_elems, sp.span, kbuf);
-    }
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-__global__ void k_fill_bbox(int32_t* bbox, int64_t n)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { bbox[4 * i + 0] = 0x7fffffff; bbox[4 * i + 1] = -1; bbox[4 * i + 2] = 0x7fffffff; bbox[4 * i + 3] = -1; }
-}
-
-int ims_fft_spike_table(const ims_spikes_t* spikes, const int32_t* row_ptr_dev, int32_t* row_count_dev, int32_t* col_dev, double* val_dev,
-                        void* stream)
-{
-    if (!spikes) return set_err(IMS_ERR_ARG, "spikes is NULL");
-    if (spikes->cutoff < 0 || spikes->cutoff > 32767 || !(spikes->norm > 0.0)) return set_err(IMS_ERR_ARG, "spikes: cutoff / norm out of range");
-    if (row_ptr_dev ? (!col_dev || !val_dev) : !row_count_dev) return set_err(IMS_ERR_ARG, "spike table: NULL output");
-    ims_spikes_t k = *spikes;
-    k.tab_row = nullptr; k.tab_col = nullptr; k.tab_val = nullptr;
-    const unsigned rows = 2u * (unsigned)k.cutoff + 1u;
-    hipLaunchKernelGGL(k_fft_spike_table, dim3((rows + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, k, row_ptr_dev, row_count_dev, col_dev, val_dev);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_fft_spikes(const ims_fft_params_t* params, const ims_fft_object_t* objects_dev, int64_t n_objects,
-                   const int64_t* pix_prefix_dev, int64_t n_pix, const double* rbuf_in, double* rbuf_out,
-                   int32_t* bbox_dev, void* stream)
-{
-    if (!params || !objects_dev || !pix_prefix_dev || !rbuf_in || !rbuf_out || !bbox_dev) return set_err(IMS_ERR_ARG, "NULL argument");
-    if (n_objects <= 0 || n_pix <= 0) return IMS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_fill_bbox, dim3((unsigned)((n_objects + 255) / 256)), dim3(256), 0, st, bbox_dev, n_objects);
-    const FftSpan sp = fft_span(n_pix);
-    if (params->spikes.enabled)
-        hipLaunchKernelGGL(k_fft_bbox, dim3(sp.grid), dim3(256), 0, st, *params, objects_dev, n_objects,
-                           pix_prefix_dev, n_pix, sp.span, rbuf_in, bbox_dev);
-    hipLaunchKernelGGL(k_fft_spikes, dim3(sp.grid), dim3(256), 0, st, *params, objects_dev, n_objects,
-                       pix_prefix_dev, n_pix, sp.span, rbuf_in, rbuf_out, (const int32_t*)bbox_dev, (const unsigned int*)nullptr, 0u);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_fft_spikes_listed(const ims_fft_params_t* params, const ims_fft_object_t* objects_dev, int64_t n_objects,
-                          const int64_t* pix_prefix_dev, int64_t n_pix, const double* rbuf_in, double* rbuf_out,
-                          int32_t* bbox_dev, uint64_t* list_dev, int64_t list_cap, uint32_t* count_dev, void* stream)
-{
-    if (!params || !objects_dev || !pix_prefix_dev || !rbuf_in || !rbuf_out || !bbox_dev || !list_dev || !count_dev)
-        return set_err(IMS_ERR_ARG, "NULL argument");
-    if (list_cap < 1 || list_cap > 0xffffffffLL) return set_err(IMS_ERR_ARG, "list_cap out of range");
-    if (n_objects >= (1ll << 24)) return set_err(IMS_ERR_ARG, "the listed spike step holds at most 2^24 objects");
-    if (n_objects <= 0 || n_pix <= 0) return IMS_OK;
-    if (!params->spikes.enabled) return ims_fft_spikes(params, objects_dev, n_objects, pix_prefix_dev, n_pix, rbuf_in, rbuf_out, bbox_dev, stream);
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned int cap = (unsigned int)list_cap;
-    HIP_TRY(hipMemsetAsync(count_dev, 0, sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_fill_bbox, dim3((unsigned)((n_objects + 255) / 256)), dim3(256), 0, st, bbox_dev, n_objects);
-    const FftSpan sp = fft_span(n_pix);
-    hipLaunchKernelGGL(k_fft_bbox, dim3(sp.grid), dim3(256), 0, st, *params, objects_dev, n_objects,
-                       pix_prefix_dev, n_pix, sp.span, rbuf_in, bbox_dev);
-    hipLaunchKernelGGL(k_fft_spikes_stream, dim3(sp.grid), dim3(256), 0, st, *params, objects_dev, n_objects, pix_prefix_dev, n_pix,
-                       sp.span, rbuf_in, rbuf_out, (const int32_t*)bbox_dev, (unsigned long long*)list_dev, cap, (unsigned int*)count_dev);
-    // the arms: a grid that covers the list at 256 entries per workgroup, at most 16 384 workgroups (they stride)
-    int64_t arms = (list_cap + 255) / 256;
-    if (arms > 16384) arms = 16384;
-    hipLaunchKernelGGL(k_fft_spikes_arms, dim3((unsigned)arms), dim3(256), 0, st, *params, objects_dev, rbuf_in, rbuf_out,
-                       (const int32_t*)bbox_dev, (const unsigned long long*)list_dev, cap, (const unsigned int*)count_dev);
-    // more arm pixels than the list holds: the whole step once more in one launch (returns at once otherwise)
-    hipLaunchKernelGGL(k_fft_spikes, dim3(sp.grid), dim3(256), 0, st, *params, objects_dev, n_objects, pix_prefix_dev, n_pix, sp.span,
-                       rbuf_in, rbuf_out, (const int32_t*)bbox_dev, (const unsigned int*)count_dev, cap);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_fft_finish(const ims_fft_params_t* params, const ims_fft_object_t* objects_dev, int64_t n_objects,
-                   const int64_t* pix_prefix_dev, int64_t n_pix, const double* rbuf, void* stream)
-{
-    if (!params || !objects_dev || !pix_prefix_dev || !rbuf) return set_err(IMS_ERR_ARG, "NULL argument");
-    if (!params->image) return set_err(IMS_ERR_ARG, "image is NULL");
-    if (n_objects <= 0 || n_pix <= 0) return IMS_OK;
-    const FftSpan sp = fft_span(n_pix);
-    hipLaunchKernelGGL(k_fft_finish, dim3(sp.grid), dim3(256), 0, (hipStream_t)stream, *params, objects_dev,
-                       n_objects, pix_prefix_dev, n_pix, sp.span, rbuf);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_sensor_pixel_areas(const ims_sensor_t* sensor_dev, const ims_sensor_t* sensor_host, int32_t slot,
-                           double* area_dev, long long* sum_q32_dev, void* stream)
-{
-    if (!sensor_dev || !area_dev || !sum_q32_dev) return set_err(IMS_ERR_ARG, "NULL argument");
-    if (!sensor_host || !sensor_host->bf_slots) return set_err(IMS_ERR_ARG, "sensor_host/bf_slots is NULL (host copy of the slot table required)");
-    if (slot < 0 || slot >= sensor_host->n_bf_slots) return set_err(IMS_ERR_ARG, "slot out of range");
-    const ims_bf_slot_t& b = sensor_host->bf_slots[slot];
-    const int64_t n = (int64_t)b.nx * b.ny;
-    if (n <= 0) return IMS_OK;
-    hipLaunchKernelGGL(k_pixel_areas, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sensor_dev, slot,
-                       area_dev, sum_q32_dev);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_flat_add(const double* area_dev, const double* base_dev, double level, double inv_mean_area, uint64_t seed,
-                 int64_t iteration, int32_t nx, int32_t ny, double* image_dev, double* delta_dev, void* stream)
-{
-    if (!image_dev) return set_err(IMS_ERR_ARG, "image is NULL");
-    if (nx <= 0 || ny <= 0) return IMS_OK;
-    const int64_t n = (int64_t)nx * ny;
-    hipLaunchKernelGGL(k_flat_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, area_dev, base_dev,
-                       level, inv_mean_area, seed, iteration, nx, ny, image_dev, delta_dev);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_image_add(double* dst, const double* src, int64_t n, void* stream)
-{
-    if (!dst || !src) return set_err(IMS_ERR_ARG, "dst/src is NULL");
-    if (n <= 0) return IMS_OK;
-    hipLaunchKernelGGL(k_image_add, dim3(grid_for_pool(n)), dim3(256), 0, (hipStream_t)stream, dst, src, n);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_paint_cosmic_rays(double* image_dev, int32_t nx, int32_t ny, const ims_cr_span_t* spans_dev, int64_t n_spans,
-                          const double* values_dev, int64_t n_values, const ims_cr_hit_t* hits_dev, const int64_t* layer_first,
-                          int32_t n_layers, void* stream)
-{
-    if (n_layers < 0 || (n_layers > 0 && !layer_first)) return set_err(IMS_ERR_ARG, "cosmic rays: bad layer list");
-    if (n_layers == 0 || layer_first[n_layers] == 0) return IMS_OK;
-    if (!image_dev || !spans_dev || !values_dev || !hits_dev) return set_err(IMS_ERR_ARG, "cosmic rays: image / spans / values / hits is NULL");
-    if (nx < 1 || ny < 1 || n_spans < 1 || n_spans > 0x7fffffffLL || n_values < 1)
-        return set_err(IMS_ERR_ARG, "cosmic rays: empty image or catalog");
-    if (layer_first[0] != 0) return set_err(IMS_ERR_ARG, "cosmic rays: layer_first[0] must be 0");
-    for (int32_t l = 0; l < n_layers; ++l)
-        if (layer_first[l + 1] < layer_first[l] || layer_first[l + 1] - layer_first[l] > 0x7fffffffLL)
-            return set_err(IMS_ERR_ARG, "cosmic rays: layer_first must be non-decreasing");
-    hipStream_t st = (hipStream_t)stream;
-    for (int32_t l = 0; l < n_layers; ++l) {
-        const int64_t n = layer_first[l + 1] - layer_first[l];
-        if (n == 0) continue;
-        hipLaunchKernelGGL(k_paint_cosmic_rays, dim3((unsigned)n), dim3(64), 0, st, image_dev, nx, ny, spans_dev, n_spans, values_dev,
-                           n_values, hits_dev + layer_first[l]);
-    }
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_object_spectra(const double* grid, const double* thr, const double* ext_a, const double* ext_b, int32_t n_grid, double band_hi,
-                       const double* sed_wave, const double* sed_fphotons, const int64_t* sed_offset, int32_t n_sed,
-                       const int32_t* sed_id, const double* redshift, const double* mw_av, const double* mw_rv, int64_t n_obj,
-                       int32_t n_pts, double* flux, double* tables, int64_t row_offset, void* stream)
-{
-    if (n_obj < 0 || row_offset < 0) return set_err(IMS_ERR_ARG, "object spectra: negative object count or row offset");
-    if (n_obj == 0) return IMS_OK;
-    if (!grid || !thr || !ext_a || !ext_b || !sed_offset || !sed_id || !redshift || !mw_av || !mw_rv || !flux || !tables)
-        return set_err(IMS_ERR_ARG, "object spectra: an array is NULL");
-    if (n_sed < 0 || (n_sed > 0 && (!sed_wave || !sed_fphotons))) return set_err(IMS_ERR_ARG, "object spectra: the SED library is NULL");
-    if (n_grid < 2 || n_pts < 2) return set_err(IMS_ERR_ARG, "object spectra: the band grid and the tables need two points at least");
-    if ((int64_t)n_grid * SED_WAVES * (int64_t)sizeof(double) > SED_MAX_LDS) {
-        snprintf(g_err, sizeof(g_err), "object spectra: a band grid of %d points does not fit the %d doubles of LDS a wavefront has "
-                 "(a coarser step or a narrower band)", (int)n_grid, (int)(SED_MAX_LDS / (SED_WAVES * sizeof(double))));
-        return IMS_ERR_UNSUPPORTED;
-    }
-    const int64_t blocks = (n_obj + SED_WAVES - 1) / SED_WAVES;
-    if (blocks > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "object spectra: too many objects for one launch");
-    SedArgs A;
-    A.grid = grid; A.thr = thr; A.ext_a = ext_a; A.ext_b = ext_b;
-    A.wave = sed_wave; A.fphot = sed_fphotons; A.offset = sed_offset;
-    A.sed_id = sed_id; A.redshift = redshift; A.mw_av = mw_av; A.mw_rv = mw_rv;
-    A.flux = flux; A.tables = tables + row_offset * (int64_t)n_pts;
-    A.band_hi = band_hi; A.n_obj = n_obj;
-    A.n_grid = n_grid; A.n_sed = n_sed; A.n_pts = n_pts; A.lds_stride = n_grid;
-    hipLaunchKernelGGL(k_object_spectra, dim3((unsigned)blocks), dim3(64 * SED_WAVES), (size_t)n_grid * SED_WAVES * sizeof(double),
-                       (hipStream_t)stream, A);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_image_to_float(const double* src, float* dst, int64_t n, void* stream)
-{
-    if (!dst || !src) return set_err(IMS_ERR_ARG, "dst/src is NULL");
-    if (n <= 0) return IMS_OK;
-    hipLaunchKernelGGL(k_image_to_float, dim3(grid_for_pool(n)), dim3(256), 0, (hipStream_t)stream, src, dst, n);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_build_object_table(const ims_catalog_t* cat, const ims_optics_t* optics_dev, ims_object_t* rows_dev,
-                           ims_object_meta_t* meta_dev, void* stream)
-{
-    if (!cat || !optics_dev || !rows_dev || !meta_dev) return set_err(IMS_ERR_ARG, "NULL argument");
-    if (cat->n < 0) return set_err(IMS_ERR_ARG, "negative catalog length");
-    if (cat->n == 0) return IMS_OK;
-    if (!cat->x || !cat->y || !cat->nominal_flux || !cat->kind || !cat->hlr || !cat->q || !cat->pa || !cat->prof_table)
-        return set_err(IMS_ERR_ARG, "catalog column is NULL");
-    if ((cat->g1 != nullptr) != (cat->g2 != nullptr) || (cat->g1 != nullptr) != (cat->mu != nullptr))
-        return set_err(IMS_ERR_ARG, "g1, g2 and mu come together");
-    if (!cat->star_size || cat->n_star_size <= 0 || !cat->gal_radius || cat->n_gal_radius <= 0)
-        return set_err(IMS_ERR_ARG, "star_size / gal_radius table missing");
-    if (!(cat->pixel_scale > 0.0) || !(cat->dg_stepk > 0.0) || cat->nmax <= 0) return set_err(IMS_ERR_ARG, "pixel_scale / dg_stepk / nmax");
-    hipLaunchKernelGGL(k_build_object_table, dim3((unsigned)((cat->n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *cat, optics_dev,
-                       rows_dev, meta_dev);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_patch_stamp_sizes(ims_object_t* rows_dev, ims_object_meta_t* meta_dev, const int64_t* index_dev, const int32_t* size_dev,
-                          int64_t n, void* stream)
-{
-    if (n <= 0) return IMS_OK;
-    if (!rows_dev || !meta_dev || !index_dev || !size_dev) return set_err(IMS_ERR_ARG, "NULL argument");
-    hipLaunchKernelGGL(k_patch_stamp_sizes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows_dev, meta_dev, index_dev,
-                       size_dev, n);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_gather_rows(const ims_object_t* rows_dev, const int64_t* index_dev, const int64_t* first_dev, const int64_t* count_dev,
-                    const int32_t* bf_state_dev, int32_t clear_flags, ims_object_t* dst_dev, int64_t n, void* stream)
-{
-    if (n <= 0) return IMS_OK;
-    if (!rows_dev || !index_dev || !dst_dev) return set_err(IMS_ERR_ARG, "NULL argument");
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows_dev, index_dev, first_dev,
-                       count_dev, bf_state_dev, clear_flags, dst_dev, n);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-static int opd_run(const ims_opd_t* P, const ims_optics_t* optics_dev, bool pert, void* stream)
-{
-    if (!P || !optics_dev) return set_err(IMS_ERR_ARG, "opd / optics is NULL");
-    if (P->n_fields < 0) return set_err(IMS_ERR_ARG, "opd: negative n_fields");
-    if (P->nx < 1 || P->nx > IMS_OPD_MAX_NX) return set_err(IMS_ERR_ARG, "opd: nx out of range");
-    if (P->reference != IMS_OPD_REF_CHIEF && P->reference != IMS_OPD_REF_MEAN) return set_err(IMS_ERR_ARG, "opd: unknown reference");
-    if (P->jmax < 0 || P->jmax > IMS_OPD_MAX_J) return set_err(IMS_ERR_ARG, "opd: jmax out of range (0 .. 66)");
-    if (!(P->dx > 0.0) || !(P->wavelength > 0.0) || !(P->sphere_radius > 0.0))
-        return set_err(IMS_ERR_ARG, "opd: dx, wavelength and sphere_radius must be positive");
-    if (P->n_fields == 0) return IMS_OK;
-    if (!P->dirs || !P->opd || !P->scratch) return set_err(IMS_ERR_ARG, "opd: dirs / opd / scratch is NULL");
-    if (P->jmax > 0) {
-        if (!P->zk_poly || !P->zk_m || !P->zk_ata || !P->zk_atw) return set_err(IMS_ERR_ARG, "opd: Zernike table or output is NULL");
-        if (!(P->r_outer > 0.0) || !(P->eps >= 0.0 && P->eps < 1.0)) return set_err(IMS_ERR_ARG, "opd: r_outer > 0 and 0 <= eps < 1");
-    }
-    const OpdLayout L = opd_layout(*P);
-    if ((L.n_rays + OPD_WG - 1) / OPD_WG > 0x7fffffffLL || L.nblk > 0x7fffffffLL || P->n_fields > 65535)
-        return set_err(IMS_ERR_ARG, "opd: too many rays or fields for one call");
-    hipStream_t s = (hipStream_t)stream;
-    const ims_opd_t A = *P;
-    const dim3 per_block((unsigned)L.nblk, (unsigned)P->n_fields);
-    if (pert) hipLaunchKernelGGL((k_opd_trace<true>), dim3((unsigned)((L.n_rays + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, optics_dev, L);
-    else hipLaunchKernelGGL((k_opd_trace<false>), dim3((unsigned)((L.n_rays + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, optics_dev, L);
-    if (P->reference == IMS_OPD_REF_MEAN) hipLaunchKernelGGL(k_opd_hit_partial, per_block, dim3(OPD_WG), 0, s, A, L);
-    hipLaunchKernelGGL(k_opd_field, dim3((unsigned)P->n_fields), dim3(OPD_WG), 0, s, A, L, 0);
-    hipLaunchKernelGGL(k_opd_sphere, per_block, dim3(OPD_WG), 0, s, A, L);
-    hipLaunchKernelGGL(k_opd_field, dim3((unsigned)P->n_fields), dim3(OPD_WG), 0, s, A, L, 1);
-    const int64_t n_map = (int64_t)P->n_fields * L.npix;
-    hipLaunchKernelGGL(k_opd_map, dim3((unsigned)((n_map + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, L);
-    if (P->jmax > 0) {
-        hipLaunchKernelGGL(k_opd_zk_normal, dim3((unsigned)L.nchunk, (unsigned)P->n_fields), dim3(OPD_WG), 0, s, A, L);
-        const int64_t n_ent = (int64_t)P->n_fields * L.nent;
-        hipLaunchKernelGGL(k_opd_zk_final, dim3((unsigned)((n_ent + OPD_WG - 1) / OPD_WG)), dim3(OPD_WG), 0, s, A, L);
-    }
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_opd(const ims_opd_t* P, const ims_optics_t* optics_dev, void* stream)
-{
-    return opd_run(P, optics_dev, false, stream);
-}
-
-int ims_opd_perturbed(const ims_opd_t* P, const ims_optics_perturbed_t* optics_dev, void* stream)
-{
-    return opd_run(P, optics_dev ? &optics_dev->optics : nullptr, true, stream);
-}
-
-static int trace_field_points_run(const ims_optics_t* optics_dev, bool pert, const double* thx, const double* thy, int64_t n,
-                                  double wave_nm, const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out,
-                                  void* stream)
-{
-    if (n < 0) return set_err(IMS_ERR_ARG, "trace_field_points: negative n");
-    if (n == 0) return IMS_OK;
-    if (!optics_dev || !thx || !thy || !pupil_xy || !xy_out || !ngood_out) return set_err(IMS_ERR_ARG, "trace_field_points: NULL argument");
-    if (n > 0x7fffffffLL) return set_err(IMS_ERR_ARG, "trace_field_points: too many field points for one call");
-    if (n_rays < 1 || n_rays > IMS_TRACE_MAX_RAYS) return set_err(IMS_ERR_ARG, "trace_field_points: n_rays out of range");
-    if (!(wave_nm > 0.0)) return set_err(IMS_ERR_ARG, "trace_field_points: the wavelength must be positive");
-    hipStream_t s = (hipStream_t)stream;
-    if (pert) hipLaunchKernelGGL((k_trace_field_points<true>), dim3((unsigned)n), dim3(OPD_WG), 0, s, optics_dev, thx, thy, wave_nm,
-                                 pupil_xy, (int)n_rays, xy_out, ngood_out);
-    else hipLaunchKernelGGL((k_trace_field_points<false>), dim3((unsigned)n), dim3(OPD_WG), 0, s, optics_dev, thx, thy, wave_nm,
-                            pupil_xy, (int)n_rays, xy_out, ngood_out);
-    HIP_TRY(hipGetLastError());
-    return IMS_OK;
-}
-
-int ims_trace_field_points(const ims_optics_t* optics_dev, const double* thx, const double* thy, int64_t n, double wave_nm,
-                           const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out, void* stream)
-{
-    return trace_field_points_run(optics_dev, false, thx, thy, n, wave_nm, pupil_xy, n_rays, xy_out, ngood_out, stream);
-}
-
-int ims_trace_field_points_perturbed(const ims_optics_perturbed_t* optics_dev, const double* thx, const double* thy, int64_t n,
-                                     double wave_nm, const double* pupil_xy, int32_t n_rays, double* xy_out, int32_t* ngood_out,
-                                     void* stream)
-{
-    return trace_field_points_run(optics_dev ? &optics_dev->optics : nullptr, true, thx, thy, n, wave_nm, pupil_xy, n_rays, xy_out,
-                                  ngood_out, stream);
-}
-
-}  // extern "C"
-
+#include "ims_image.h"          // LSST_Flat and image utilities: pixel areas, flats, image add / convert, cosmic rays
+#include "ims_fft_branch.h"     // the FFT branch: k-space fill, hipFFT plan cache and inverse, diffraction spikes, finish
+#include "ims_table.h"          // the object table on the device: build, patch stamp sizes, gather rows
+#include "ims_plan_run.h"       // plan items, the LSST_Image launch planner (ims_plan.h) bound and run, joint runs of a visit
+#include "ims_opd.h"            // wavefront maps, annular-Zernike normal equations and field-point traces
+#include "ims_sed.h"            // per-object SEDs through the bandpass
 #include "ims_readout.h"        // CCD readout: bleed trails, amplifier segments, CTE, noise and digitisation
 #include "ims_screen.h"         // phase-screen pre-pass
 #include "ims_derive.h"         // derived constants of the descriptors (host only)

@@ -79,6 +79,36 @@ def test_tuning_block_is_the_only_way_to_change_which_kernels_the_library_launch
             assert "os.environ" not in open(os.path.join(pkg, f)).read(), f
 
 
+def test_the_file_map_of_design_md_names_every_file_of_csrc_and_every_entry_point_has_one_home():
+    """DESIGN.md's table "File under `imsim_amd/csrc/`" lists exactly the files of csrc/; every exported name is defined once in
+    them (a line `<return type> NAME(` at column 0); and the one translation unit includes every other file, directly or through
+    ims_photon.h (ims_math.h, ims_optical.h) and ims_plan_run.h (ims_plan.h).  Text only."""
+    csrc = os.path.join(ROOT, "imsim_amd", "csrc")
+    files = sorted(os.listdir(csrc))
+    text = {f: open(os.path.join(csrc, f)).read() for f in files}
+    design = open(os.path.join(ROOT, "DESIGN.md")).read().split("\n")
+    start = next(k for k, line in enumerate(design) if line.startswith("| File under `imsim_amd/csrc/` |"))
+    assert design[start + 1].startswith("|---")
+    listed = []
+    for line in design[start + 2:]:
+        m = re.match(r"\| `([^`]+)` \|", line)
+        if not m:
+            break
+        listed.append(m.group(1))
+    assert len(listed) == len(set(listed)), "a file is listed twice"
+    assert sorted(listed) == files
+    for name in _abi.EXPORTS:
+        homes = [f for f in files for _ in re.finditer(rf"^(?:[A-Za-z_]\w*[ *]+)+{name}\(", text[f], re.M)]
+        assert len(homes) == 1, (name, homes)
+
+    def includes(f):
+        return set(re.findall(r'^#include "(ims\w*\.h)"', text[f], re.M))
+    direct = includes("imsim_hip.hip")
+    assert {"ims_photon.h", "ims_plan_run.h"} <= direct
+    assert {"ims_math.h", "ims_optical.h"} <= includes("ims_photon.h") and "ims_plan.h" in includes("ims_plan_run.h")
+    assert direct | {"ims_math.h", "ims_optical.h", "ims_plan.h", "imsim_hip.hip"} == set(files)
+
+
 def test_joint_run_entry_points_check_their_arguments_before_any_hip_call():
     """ims_plan_run_deferred / ims_plans_run_joint / ims_plan_join (the CCDs of a visit side by side): argument errors are
     reported without touching the GPU; an empty list of plans is a no-op."""
